@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """P2RNet train-step benchmark on MI355X (contract in the task brief).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A step = one full train step of P2RNet on one batch of synthetic pose sequences
@@ -13,20 +13,27 @@ Workload = BASELINE.json configs[2]: bs=32 per GPU, T=1024, J=53 (weak scaling).
 
 The per-rank batch comes through the loader the epoch loops use (`P2RNet_dataloader`, with a
 `DistributedSampler` shard per rank when N > 1) over a seeded in-memory synthetic dataset.  `value` is
-measured with that batch resident in HBM (contract); the same K steps are then repeated with the
-reference's `to_device` inside the step -- the batch (6.5 MB per sample) crossing PCIe from pinned
-host memory each step, prefetched one step ahead on a side stream -- and reported under `h2d`.
+measured with that batch resident in HBM (contract).
+
+A plain run sets up, runs W warm-up steps, times the K steps, writes the outputs of the last timed step if
+`--dump-outputs DIR` is given (dump_outputs: losses, parameters, gradients, BatchNorm statistics as DIR/<name>.npy)
+and prints the line with the contract keys, `step_ms`, `config` and `step_roofline`.  Everything else runs only under
+`--full`, after the headline steps (which are therefore the same steps, with the same outputs, in both kinds of run):
+the verification at the bench shape, the same K steps with the reference's `to_device` inside the step -- the batch
+(6.5 MB per sample) crossing PCIe from pinned host memory each step, prefetched one step ahead on a side stream --
+reported under `h2d`, and the instrumented, split16, kernel and CPU measurements below.
 
 Rank 0 prints ONE JSON line.  Besides the contract keys it carries
   step_ms      -- median / p10 / p90 of the per-step device time (events between steps, no host sync);
+  step_roofline-- the whole step: MFMA FLOPs issued per step (stored PMC profile) over this run's step time;
+and with --full
   h2d          -- the same run with the batch copied host -> device every step (pinned, prefetched);
-  verify       -- what was checked at the bench shape BEFORE timing (finite losses of a train step; sample 0 of the
-                  full batch against the same sample run alone with running-statistics BatchNorm);
+  verify       -- what was checked at the bench shape after the headline steps (finite losses of a train step; sample 0
+                  of the full batch against the same sample run alone with running-statistics BatchNorm);
   roofline     -- the dominant kernel (gcn3_kernel: graph-conv forward + data gradient) against the fp32 MFMA roof: MFMA
                   FLOPs the kernel ISSUES per launch / its average duration INSIDE the step (HIP events around every
                   launch of instrumented steps that follow the timed region);
   mfma_kernels -- the same for the other MFMA kernels of the ST-GCN blocks (in-step durations, issued FLOPs);
-  step_roofline-- the whole step: MFMA FLOPs issued per step (stored PMC profile) over this run's step time;
   ddp          -- N > 1 only: per-rank step times, and the step time with the gradient all-reduce switched off
                   (`no_sync`) next to the one with it = the all-reduce time that is NOT hidden under the backward pass;
   split16      -- the SAME K steps in the opt-in split16 arithmetic of the ST-GCN kernels (pose2room_amd.p2rnet.math_mode:
@@ -437,6 +444,37 @@ def build_trainer_cpu(frames):
     return Trainer(cfg, net, load_optimizer(cfg.config, net), torch.device('cpu')), cfg
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, trainer, losses):
+    """What the last timed step hands its caller, as <path>/<name>.npy: the logged losses `train_step` returns
+    (`loss.<key>`, float64) and the model state the step leaves behind -- every parameter after the optimiser step
+    (`param.<name>`), its gradient from the step's backward pass after clipping (`grad.<name>`) and the floating-point
+    buffers, i.e. the BatchNorm running statistics the step updated (`buffer.<name>`), each in float32 or float64 as
+    held.  ~16.5 MB whatever the batch and frame count: the sizes are those of the model."""
+    import numpy as np
+    net = trainer.net.module
+    arrays = {'loss.' + k: np.asarray(v, dtype=np.float64) for k, v in losses.items()}
+
+    def host(t):
+        t = t.detach()
+        return (t.double() if t.dtype == torch.float64 else t.float()).cpu().numpy()
+
+    for name, p in net.named_parameters():
+        arrays['param.' + name] = host(p)
+        if p.grad is not None:
+            arrays['grad.' + name] = host(p.grad)
+    for name, b in net.named_buffers():
+        if b.is_floating_point():
+            arrays['buffer.' + name] = host(b)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f'{total} bytes of outputs exceed the {DUMP_LIMIT_BYTES}-byte dump limit'
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -444,6 +482,12 @@ def main():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--batch', type=int, default=32, help='per-GPU batch (BASELINE: 32)')
     ap.add_argument('--frames', type=int, default=1024, help='T (BASELINE: 1024)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed as DIR/<name>.npy (dump_outputs)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline steps, also run the verification, the H2D repeat, the in-step kernel '
+                         'rooflines, the all-reduce cost (N > 1), the split16 leg, the kernel microbenchmarks and the '
+                         'CPU baseline (the three --no-* options below drop the last three)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-microbench', action='store_true')
     ap.add_argument('--no-split16', action='store_true', help='skip the labelled split16 sub-measurement')
@@ -487,7 +531,6 @@ def main():
     def step():
         return trainer.train_step(dict(batch))
 
-    verify = verify_bench_shape(trainer, batch)      # not timed, not part of the warm-up count
     for _ in range(max(args.warmup - 1, 0)):
         step()
     # Python's cyclic GC: the first full (generation-2) collection of a process walks every object torch and the
@@ -525,94 +568,100 @@ def main():
         return dt, out, {'median': round(q(0.5), 3), 'p10': round(q(0.1), 3), 'p90': round(q(0.9), 3)}
 
     elapsed, last, step_ms = timed(step)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer, last)
 
-    # ---- the same steps with the reference's to_device inside the step (models/p2rnet/training.py:100-107): the batch
-    # sits in pinned host memory and is copied one step ahead on a side stream
-    pinned = {k: (v.pin_memory() if torch.is_tensor(v) else v) for k, v in host_batch.items()}
-    h2d_bytes = sum(v.numel() * v.element_size() for v in pinned.values() if torch.is_tensor(v))
-    copy_stream = torch.cuda.Stream(device)
-    state = {}
+    ddp_info = split16 = None
+    if args.full:
+        # what was checked at the bench shape (not timed; after the headline steps, so that they and their outputs are
+        # the same with and without --full)
+        verify = verify_bench_shape(trainer, batch)
 
-    def prefetch():
-        with torch.cuda.stream(copy_stream):
-            state['next'] = {k: (v.to(device, non_blocking=True) if torch.is_tensor(v) else v) for k, v in pinned.items()}
-            state['ready'] = torch.cuda.Event()
-            state['ready'].record(copy_stream)
+        # ---- the same steps with the reference's to_device inside the step (models/p2rnet/training.py:100-107): the batch
+        # sits in pinned host memory and is copied one step ahead on a side stream
+        pinned = {k: (v.pin_memory() if torch.is_tensor(v) else v) for k, v in host_batch.items()}
+        h2d_bytes = sum(v.numel() * v.element_size() for v in pinned.values() if torch.is_tensor(v))
+        copy_stream = torch.cuda.Stream(device)
+        state = {}
 
-    def step_h2d():
-        cur, ready = state['next'], state['ready']
-        torch.cuda.current_stream(device).wait_event(ready)
-        for v in cur.values():
-            if torch.is_tensor(v):
-                v.record_stream(torch.cuda.current_stream(device))
-        prefetch()                                   # the next batch crosses PCIe under this step's kernels
-        return trainer.train_step(cur)
+        def prefetch():
+            with torch.cuda.stream(copy_stream):
+                state['next'] = {k: (v.to(device, non_blocking=True) if torch.is_tensor(v) else v) for k, v in pinned.items()}
+                state['ready'] = torch.cuda.Event()
+                state['ready'].record(copy_stream)
 
-    prefetch()
-    step_h2d()
-    elapsed_h2d, _, step_ms_h2d = timed(step_h2d)
+        def step_h2d():
+            cur, ready = state['next'], state['ready']
+            torch.cuda.current_stream(device).wait_event(ready)
+            for v in cur.values():
+                if torch.is_tensor(v):
+                    v.record_stream(torch.cuda.current_stream(device))
+            prefetch()                                   # the next batch crosses PCIe under this step's kernels
+            return trainer.train_step(cur)
 
-    # instrumented steps (events around the MFMA kernels' launches): every rank runs them -- they contain the gradient
-    # all-reduce -- rank 0 reports
-    roof, rows = mfma_rooflines(trainer, batch, args.batch, args.frames)
+        prefetch()
+        step_h2d()
+        elapsed_h2d, _, step_ms_h2d = timed(step_h2d)
 
-    ddp_info = None
-    if world > 1:
-        # (1) spread of the ranks' own step times; (2) the same K steps with the gradient all-reduce switched off
-        # (DDP.no_sync: hooks do not fire, gradients stay local) = what the all-reduce costs on top of a step, i.e. the
-        # part of it that is not hidden under the backward pass.  Runs last: the ranks' weights diverge under no_sync.
-        mine = torch.tensor([step_ms['median']], dtype=torch.float64, device=device)
-        every = [torch.zeros_like(mine) for _ in range(world)]
-        dist.all_gather(every, mine)
-        per_rank = [round(float(t.item()), 3) for t in every]
+        # instrumented steps (events around the MFMA kernels' launches): every rank runs them -- they contain the gradient
+        # all-reduce -- rank 0 reports
+        roof, rows = mfma_rooflines(trainer, batch, args.batch, args.frames)
 
-        def step_no_sync():
-            with trainer.net.no_sync():
-                return trainer.train_step(dict(batch))
-        step_no_sync()
-        # the two forms back to back, twice, in the same thermal / clock state (a difference against the headline block,
-        # timed minutes earlier, is mostly noise: each number is a max over ranks with ~1 % spread)
-        rounds = []
-        for _ in range(2):
-            e_sync, _, _ = timed(step)
-            e_ns, _, _ = timed(step_no_sync)
-            rounds.append((e_sync / args.steps * 1e3, e_ns / args.steps * 1e3))
-        exposed = [a - b for a, b in rounds]
-        ddp_info = {'rank_step_ms_median': per_rank, 'rank_spread_ms': round(max(per_rank) - min(per_rank), 3),
-                    'ms_per_step_no_sync': round(min(b for _, b in rounds), 3),
-                    'ms_per_step_sync_same_block': round(min(a for a, _ in rounds), 3),
-                    'allreduce_exposed_ms_per_step': round(max(0.0, min(exposed)), 3),
-                    'allreduce_exposed_rounds_ms': [round(e, 3) for e in exposed],
-                    'how': '2 x (K steps with the gradient all-reduce, K steps under DDP.no_sync()) back to back; exposed = '
-                           'the smaller difference, clamped at 0 (noise floor ~1 % of a step); the 80-byte logging '
-                           'all-reduce is in both', 'gradient_bytes_per_step': 8176132,
-                    'backend': dist.get_backend()}
+        if world > 1:
+            # (1) spread of the ranks' own step times; (2) the same K steps with the gradient all-reduce switched off
+            # (DDP.no_sync: hooks do not fire, gradients stay local) = what the all-reduce costs on top of a step, i.e. the
+            # part of it that is not hidden under the backward pass.  Runs last: the ranks' weights diverge under no_sync.
+            mine = torch.tensor([step_ms['median']], dtype=torch.float64, device=device)
+            every = [torch.zeros_like(mine) for _ in range(world)]
+            dist.all_gather(every, mine)
+            per_rank = [round(float(t.item()), 3) for t in every]
 
-    # ---- the same steps in the opt-in split16 arithmetic (every rank runs them: they contain the gradient all-reduce).
-    # After everything the exact path needs; the mode is switched back before the line is printed.
-    split16 = None
-    if not args.no_split16 and args.frames % 16 == 0:
-        from pose2room_amd.p2rnet import math_mode
-        math_mode.set_mode('split16')
-        try:
-            verify16 = verify_bench_shape(trainer, batch)
-            for _ in range(args.warmup):
-                step()
-            passes0 = math_mode.FALLBACK_PASSES
-            elapsed16, last16, step_ms16 = timed(step)
-            passes = (math_mode.FALLBACK_PASSES - passes0) / float(args.steps)
-            roof16, rows16 = split16_rooflines(trainer, batch, args.batch, args.frames)
-        finally:
-            math_mode.set_mode('exact')
-            math_mode.reset()
-        split16 = {'value': round(world * args.batch * args.steps / elapsed16, 3), 'unit': 'samples/s',
-                   'ms_per_step': round(elapsed16 / args.steps * 1e3, 3), 'step_ms': step_ms16, 'verify': verify16,
-                   'dtype': 'f32 products as three fp16 MFMA products of two-part operands (22 of 24 significand bits), '
-                            'fp32 accumulation -- ST-GCN graph conv forward / data gradient and temporal conv forward / data '
-                            'gradient; every other kernel exact fp32',
-                   'loss_total': round(float(last16['total']), 4), 'range_word_fallback_passes_per_step': passes,
-                   'roofline': roof16, 'kernels': rows16, 'speedup_vs_exact': round(elapsed / elapsed16, 4),
-                   'how': 'P2R_MATH=split16 / math_mode.set_mode; same trainer, same batch, same K and W as the headline'}
+            def step_no_sync():
+                with trainer.net.no_sync():
+                    return trainer.train_step(dict(batch))
+            step_no_sync()
+            # the two forms back to back, twice, in the same thermal / clock state (a difference against the headline block,
+            # timed minutes earlier, is mostly noise: each number is a max over ranks with ~1 % spread)
+            rounds = []
+            for _ in range(2):
+                e_sync, _, _ = timed(step)
+                e_ns, _, _ = timed(step_no_sync)
+                rounds.append((e_sync / args.steps * 1e3, e_ns / args.steps * 1e3))
+            exposed = [a - b for a, b in rounds]
+            ddp_info = {'rank_step_ms_median': per_rank, 'rank_spread_ms': round(max(per_rank) - min(per_rank), 3),
+                        'ms_per_step_no_sync': round(min(b for _, b in rounds), 3),
+                        'ms_per_step_sync_same_block': round(min(a for a, _ in rounds), 3),
+                        'allreduce_exposed_ms_per_step': round(max(0.0, min(exposed)), 3),
+                        'allreduce_exposed_rounds_ms': [round(e, 3) for e in exposed],
+                        'how': '2 x (K steps with the gradient all-reduce, K steps under DDP.no_sync()) back to back; exposed = '
+                               'the smaller difference, clamped at 0 (noise floor ~1 % of a step); the 80-byte logging '
+                               'all-reduce is in both', 'gradient_bytes_per_step': 8176132,
+                        'backend': dist.get_backend()}
+
+        # ---- the same steps in the opt-in split16 arithmetic (every rank runs them: they contain the gradient all-reduce).
+        # After everything the exact path needs; the mode is switched back before the line is printed.
+        if not args.no_split16 and args.frames % 16 == 0:
+            from pose2room_amd.p2rnet import math_mode
+            math_mode.set_mode('split16')
+            try:
+                verify16 = verify_bench_shape(trainer, batch)
+                for _ in range(args.warmup):
+                    step()
+                passes0 = math_mode.FALLBACK_PASSES
+                elapsed16, last16, step_ms16 = timed(step)
+                passes = (math_mode.FALLBACK_PASSES - passes0) / float(args.steps)
+                roof16, rows16 = split16_rooflines(trainer, batch, args.batch, args.frames)
+            finally:
+                math_mode.set_mode('exact')
+                math_mode.reset()
+            split16 = {'value': round(world * args.batch * args.steps / elapsed16, 3), 'unit': 'samples/s',
+                       'ms_per_step': round(elapsed16 / args.steps * 1e3, 3), 'step_ms': step_ms16, 'verify': verify16,
+                       'dtype': 'f32 products as three fp16 MFMA products of two-part operands (22 of 24 significand bits), '
+                                'fp32 accumulation -- ST-GCN graph conv forward / data gradient and temporal conv forward / data '
+                                'gradient; every other kernel exact fp32',
+                       'loss_total': round(float(last16['total']), 4), 'range_word_fallback_passes_per_step': passes,
+                       'roofline': roof16, 'kernels': rows16, 'speedup_vs_exact': round(elapsed / elapsed16, 4),
+                       'how': 'P2R_MATH=split16 / math_mode.set_mode; same trainer, same batch, same K and W as the headline'}
 
     if rank == 0:
         ms = elapsed / args.steps * 1e3
@@ -622,25 +671,26 @@ def main():
             'unit': 'samples/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
             'ms_per_step': round(ms, 3), 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
             'dtype': 'f32', 'data': 'synthetic', 'step_ms': step_ms,
-            'h2d': {'value': round(world * args.batch * args.steps / elapsed_h2d, 3), 'unit': 'samples/s',
-                    'ms_per_step': round(elapsed_h2d / args.steps * 1e3, 3), 'step_ms': step_ms_h2d,
-                    'bytes_per_step': h2d_bytes,
-                    'how': 'batch copied from pinned host memory every step (reference to_device), one step ahead on a '
-                           'side stream'},
             'config': {'workload': f'P2RNet full train step, bs={args.batch}/GPU, T={args.frames}, J=53, '
                                    f'seeds=512, proposals=128'
                                    + (' (BASELINE configs[2])' if (args.batch, args.frames) == (32, 1024) else ''),
                        'input': 'P2RNet_dataloader over SyntheticPoseDataset' + (' + DistributedSampler' if world > 1 else ''),
                        'global_batch': world * args.batch, 'frames': args.frames,
                        'parallelism': f'dp{world}', 'loss_total': round(float(last['total']), 4)},
-            'verify': verify,
         }
-        if ddp_info:
-            line['ddp'] = ddp_info
-        if split16:
-            line['split16'] = split16
-        line['roofline'] = roof
-        line['mfma_kernels'] = rows
+        if args.full:
+            line['h2d'] = {'value': round(world * args.batch * args.steps / elapsed_h2d, 3), 'unit': 'samples/s',
+                           'ms_per_step': round(elapsed_h2d / args.steps * 1e3, 3), 'step_ms': step_ms_h2d,
+                           'bytes_per_step': h2d_bytes,
+                           'how': 'batch copied from pinned host memory every step (reference to_device), one step '
+                                  'ahead on a side stream'}
+            line['verify'] = verify
+            if ddp_info:
+                line['ddp'] = ddp_info
+            if split16:
+                line['split16'] = split16
+            line['roofline'] = roof
+            line['mfma_kernels'] = rows
         issued, src = step_mfma_issued(args.batch, args.frames)
         ex_tf = issued / (ms * 1e-3) / 1e12 if issued else None
         line['step_roofline'] = {
@@ -651,9 +701,9 @@ def main():
                        'the build that profile was taken on, at bs=32, T=1024, scaled by batch x frames), not a counter '
                        'read in this run; the step time is this run\'s',
             'reference_algorithmic_gflop_per_sample': gflop_per_sample(args.frames)}
-        if not args.no_microbench:
+        if args.full and not args.no_microbench:
             line['kernels'] = kernel_microbench(device)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline(args.frames)
         print(json.dumps(line), flush=True)
     if world > 1:

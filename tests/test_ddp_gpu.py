@@ -18,7 +18,7 @@ def test_bench_two_ranks_share_gpu():
     env = dict(os.environ, P2R_BENCH_SHARE_GPU='1', HSA_ENABLE_IPC_MODE_LEGACY='0')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1',
-           '--batch', '4', '--frames', '128', '--no-cpu-baseline', '--no-microbench']
+           '--batch', '4', '--frames', '128', '--full', '--no-cpu-baseline', '--no-microbench']
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
