@@ -606,6 +606,24 @@ int p2r_mdn_mix_forward(int nheads, const p2r_mix_head *heads, int B, int G, int
 int p2r_mdn_mix_backward(int nheads, const p2r_mix_head *heads, int B, int G, int L, int logit_ctot, int dlogit_ctot,
                          void *stream);
 
+/* Bernoulli-gated mixture sampling for multi-hypothesis generation (csrc/mdn_sample.hip; mdn.py:49-61 with
+ * sample_pi = True, central_tendency 'mean'), up to three heads and any number of hypotheses per call:
+ *   out[h, b, l, d] = (1 / n_h) sum_{s < n_h} sum_g [u(h,b,l,g,s) < pi[b, g, l]] (mu[g, d] + sigma[g, d] eps(h,b,l,g,s,d))
+ * with sigma = exp(log_sigma) and every draw taken from an in-kernel Philox4x32-10 stream (counter / key layout in the
+ * header comment of csrc/mdn_sample.hip).  pi (B, G, L) f32 inside a tensor of pi_ctot channels (pointer pre-offset);
+ * mu [G][D] and out (H, B, L, D) f32 (f64 == 0) or f64; log_sigma [G][D] f32.  head_id (0..255) selects the head's
+ * stream; h_offset + i is the stream index of the i-th hypothesis of the call.  n_samples: HOST array of H counts,
+ * each in 1..256.  G <= 256, D <= 4; every output element written; run-to-run bit-identical. */
+typedef struct p2r_mdn_sample_head {
+  const float *pi, *log_sigma;
+  const void *mu;
+  void *out;
+  int D, f64, head_id;
+} p2r_mdn_sample_head;
+#define P2R_MDN_SAMPLE_MAX_HEADS 3
+int p2r_mdn_sample(int nheads, const p2r_mdn_sample_head *heads, int B, int G, int L, int pi_ctot, int H,
+                   const int *n_samples, unsigned long long seed, int h_offset, void *stream);
+
 /* ---- seams of the ST-GCN backbone (csrc/seed_ops.hip) ------------------------------------------------------------ */
 
 /* frame gather in front of conv_joint (stgcn.py:142-149; conv_joint is pointwise in time, so the gather may come

@@ -120,6 +120,40 @@ class P2RNet(BaseNetwork):
             eval_dict['batch_gt_map_cls'] = assembly_gt_map_cls(parsed_gts)
         return end_points, eval_dict, parsed_predictions
 
+    def generate_hypotheses(self, data, num_hypotheses, n_samples=None, seed=None, eval=True):
+        """Multi-modal generation (the reference's `multi_mode`, proposal_net.py:56-59 / mdn.py:116-125): H hypotheses
+        of the detection for one batch, each one `generate` whose mixture heads return the mean of n_h Bernoulli-gated
+        draws.  The trunk runs once; the draws of all heads and hypotheses are one kernel launch (mdn_sample_op) and the
+        predictions of all hypotheses are parsed / NMS-ed as one H * B batch.
+          n_samples: None -> each n_h uniform in 1..99 drawn from `seed`; an int or a length-H sequence fixes them.
+          seed: None -> a 64-bit seed drawn from torch's default CPU generator (`torch.manual_seed` reproduces a call).
+        -> list of H (end_points, eval_dict, parsed_predictions) triples shaped like `generate`'s result; the
+        deterministic end points (votes, aggregation, 'pi', objectness, class scores) are shared by all of them."""
+        from ...net_utils.ap_helper import (parse_predictions, parse_groundtruths,
+                                            assembly_pred_map_cls, assembly_gt_map_cls)
+        from .. import mdn_sample_op
+        seed, ns = mdn_sample_op.resolve_draws(num_hypotheses, n_samples, seed)
+        H = len(ns)
+        xyz, features, end_points = self._votes(data)
+        end_points, stacked, _ = self.detection.generate_hypotheses(xyz, features, end_points, H, ns, seed)
+        B = end_points['aggregated_vote_xyz'].shape[0]
+        joints = data['input_joints']
+        gt_stacked = {'input_joints': joints.unsqueeze(0).expand(H, *joints.shape).reshape(H * B, *joints.shape[1:])}
+        eval_all, parsed_all = parse_predictions(stacked, gt_stacked, self.cfg.eval_config)
+        gt_map = assembly_gt_map_cls(parse_groundtruths(data, self.cfg.eval_config)) if eval else None
+        out = []
+        for h in range(H):
+            sl = slice(h * B, (h + 1) * B)
+            ep = dict(end_points)
+            for k in ('center', 'size', 'heading'):
+                ep[k] = stacked[k][sl]
+            eval_dict = assembly_pred_map_cls({'pred_mask': eval_all['pred_mask'][sl]},
+                                              {k: v[sl] for k, v in parsed_all.items()}, self.cfg.eval_config)
+            if eval:
+                eval_dict['batch_gt_map_cls'] = gt_map
+            out.append((ep, eval_dict, {k: v[sl] for k, v in parsed_all.items()}))
+        return out
+
     def loss(self, pred_data, gt_data):
         if isinstance(pred_data, tuple):
             pred_data = pred_data[0]

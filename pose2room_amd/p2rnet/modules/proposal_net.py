@@ -183,3 +183,32 @@ class ProposalNet(nn.Module):
         end_points = decode_scores(pred_center, pred_size, pred_heading, sem_obj_feature, end_points)
         end_points['pi'] = {'center': pi_center, 'size': pi_size, 'heading': pi_heading}
         return end_points, (features.transpose(1, 2).contiguous() if export_proposal_feature else None)
+
+    def generate_hypotheses(self, xyz, features, end_points, num_hypotheses, n_samples, seed):
+        """Multi-mode generation without re-running the trunk: the deterministic part (vote aggregation, stems,
+        mixture weights pi, objectness and class scores) once, then every head's Bernoulli-gated mixture draws for
+        all H hypotheses in one launch (csrc/mdn_sample.hip).  n_samples: H counts, seed: 64-bit stream key.
+        -> (end_points shared by every hypothesis, with 'pi'; stacked end points of the H * B batch for
+        `parse_predictions`, hypothesis-major; the predictions (H, B, K, D) of the centre, size and heading heads)."""
+        for gm in (self.gmm_center, self.gmm_size, self.gmm_heading):
+            if gm.mdn.hparams.central_tendency != 'mean':
+                raise NotImplementedError("generate_hypotheses samples the 'mean' central tendency only")
+        features = self._aggregate(xyz, features, end_points)
+        from .. import pw_op, mdn_sample_op
+        if USE_FUSED_HEADS and pw_op.proposal_heads_supported(self, features):
+            _, _, _, sem_obj_feature, pis = pw_op.proposal_heads(self, features, False, return_pi=True)
+        else:
+            pis = (self.gmm_center.forward(self.conv_center(features)), self.gmm_size.forward(self.conv_size(features)),
+                   self.gmm_heading.forward(self.conv_heading(features)))
+            sem_obj_feature = self.conv_sem_obj(features)
+        end_points['pi'] = {'center': pis[0], 'size': pis[1], 'heading': pis[2]}
+        sem_obj = sem_obj_feature.transpose(2, 1)
+        end_points['objectness_scores'] = sem_obj[..., 0:2]
+        end_points['sem_cls_scores'] = sem_obj[..., 2:]
+        preds = mdn_sample_op.sample([self.gmm_center.mdn, self.gmm_size.mdn, self.gmm_heading.mdn], list(pis),
+                                     n_samples, seed)
+        H, (B, _, K) = len(n_samples), sem_obj_feature.shape
+        stack = lambda t: t.unsqueeze(0).expand(H, *t.shape).reshape(H * B, *t.shape[1:])    # noqa: E731
+        stacked = decode_scores(*[p.reshape(H * B, K, -1).transpose(1, 2) for p in preds], stack(sem_obj_feature),
+                                {'aggregated_vote_xyz': stack(end_points['aggregated_vote_xyz'])})
+        return end_points, stacked, preds

@@ -112,3 +112,39 @@ def test(cfg, tester, batches, ap_device='cpu'):
             cfg.log_string('eval %s: %f' % (key, metrics[key]))
         out['metrics'].append(metrics)
     return out
+
+
+def test_multi_modal(cfg, net, batches, num_hypotheses, n_samples=None, seed=None, ap_device='cpu',
+                     dump_threshold=0.5):
+    """Multi-modal evaluation: what `num_hypotheses` reference test runs in multi mode plus
+    utils/eval/multi_modal_eval.py produce, from one trunk pass per batch (`P2RNet.generate_hypotheses`).
+    Hypothesis h plays run h: its sample counts n_h are fixed for all batches (drawn once from `seed` when None, as
+    the reference draws one count per run), one `APCalculator` per IoU threshold collects its detections, and its
+    confident boxes (dump_threshold: the reference's generation.dump_threshold) are its dump records.
+    net: P2RNet (or a wrapper exposing it as `.module`).
+    -> {'best_map': (T,) max over hypotheses of each threshold's mAP, 'tmd': mean TMD over every (sample, proposal),
+        'metrics': [h][t] metric dicts, 'n_samples': [n_h], 'seed': the 64-bit seed}."""
+    from ..net_utils import multi_modal_eval as mm
+    from .mdn_sample_op import resolve_draws
+    model = getattr(net, 'module', net)
+    seed, ns = resolve_draws(num_hypotheses, n_samples, seed)
+    H = len(ns)
+    thresholds = cfg.config[cfg.config['mode']]['ap_iou_thresholds']
+    calcs = [[APCalculator(thr, getattr(cfg.dataset_config, 'class2type', None), False, device=ap_device)
+              for thr in thresholds] for _ in range(H)]
+    records = [[] for _ in range(H)]
+    model.train(False)
+    with torch.no_grad():
+        for i, data in enumerate(batches):
+            batch_seed = (seed + i * 0x9E3779B97F4A7C15) & 0xffffffffffffffff     # one stream key per batch
+            for h, (ep, eval_dict, parsed) in enumerate(model.generate_hypotheses(data, H, ns, batch_seed, eval=True)):
+                for calc in calcs[h]:
+                    calc.step(eval_dict['batch_pred_map_cls'], eval_dict['batch_gt_map_cls'])
+                records[h] += mm.confident_boxes(ep, eval_dict, parsed, dump_threshold)
+    metrics = [[c.compute_metrics() for c in row] for row in calcs]
+    best = mm.best_of_n_map([[m['mAP'] for m in row] for row in metrics])
+    for thr, v in zip(thresholds, best):
+        cfg.log_string('multi-modal (%d hypotheses) iou_thresh %f: best mAP %f' % (H, thr, v))
+    t = mm.tmd(records)
+    cfg.log_string('multi-modal TMD: %f' % t)
+    return {'best_map': best, 'tmd': t, 'metrics': metrics, 'n_samples': ns, 'seed': seed}
