@@ -12,7 +12,7 @@ import torch
 from torch.autograd import Function
 
 from .. import _lib
-from . import math_mode
+from . import handoff, math_mode
 
 
 def _rows(x):
@@ -134,17 +134,15 @@ class BNLink(object):
 
     When every use of y goes through one `gcn_op.graph_conv` call (st_gcn_block chains: y is the next block's
     input and identity branch), that op's data-gradient kernel produces the whole gradient of y, so it can also
-    emit the two per-channel sums of this BatchNorm's backward from its row epilogue (`partials`), which replaces
-    the reduction pass over the gradient and the saved input.  `grad_ptr` identifies the gradient buffer the
-    sums belong to and `grad_version` its version counter when the kernel wrote it; the BatchNorm backward uses
-    the sums only for that very buffer in that very state (a second consumer of y would make autograd hand over a
-    different tensor, or accumulate into this one in place, which bumps the counter)."""
-    __slots__ = ('u', 'mask', 'fin', 'versions', 'partials', 'grad_ptr', 'grad_version', 'used', 'ready')
+    emit the two per-channel sums of this BatchNorm's backward from its row epilogue, which replaces the reduction
+    pass over the gradient and the saved input.  It leaves them on the gradient it returns (handoff 'bn_sums'), so the
+    BatchNorm backward uses them only for that very tensor in that very state (a second consumer of y would make
+    autograd hand over a different tensor, or accumulate into this one in place, which bumps the counter)."""
+    __slots__ = ('u', 'mask', 'fin', 'versions', 'used')
 
     def __init__(self):
-        self.u = self.mask = self.fin = self.versions = self.partials = self.grad_ptr = self.grad_version = None
-        self.ready = None       # event recorded right behind the kernel that wrote the gradient and `partials`
-        self.used = 0           # how many backward passes took the sums from the link (tests)
+        self.u = self.mask = self.fin = self.versions = None
+        self.used = 0           # how many backward passes took the sums from the graph conv (tests)
 
     def attach(self, u, mask, fin):
         """The BatchNorm's saved input, ReLU mask bytes and constants.  They are plain references (the consumer is
@@ -161,31 +159,14 @@ class BNLink(object):
                 self.versions == (self.u._version, self.mask._version, self.fin._version))
 
 
-class ResLink(object):
-    """Handshake for a residual-branch gradient that is handed over UNMASKED (see `_FusedBNAct`, lazy_res): the producer
-    (this BatchNorm + residual + ReLU's backward) leaves the ReLU mask bytes and the identity (address, version counter)
-    of the tensor it returned for the residual; the one consumer (gcn_op._GraphConv.backward of the same block) takes the
-    mask for exactly that tensor.  One link per block and forward pass; nothing global."""
-    __slots__ = ('mask', 'grad_ptr', 'grad_version')
-
-    def __init__(self):
-        self.mask = self.grad_ptr = self.grad_version = None
-
-    def take(self, t):
-        """the mask for residual gradient `t`, or None when `t` is not the tensor the producer announced"""
-        if t is None or self.mask is None or self.grad_ptr != t.data_ptr() or self.grad_version != t._version:
-            return None
-        mask, self.mask, self.grad_ptr, self.grad_version = self.mask, None, None, None
-        return mask
-
-
 class _FusedBNAct(Function):
     """Train-mode BatchNorm (+res) (+ReLU).  `fin` [4, C] = (mean, invstd, scale, shift) from `finalize`.
 
-    lazy_res = a `ResLink` (only when `res` is the identity branch handed out by gcn_op.graph_conv(with_residual=True,
-    lazy_res=the same link), whose backward is the one consumer of its gradient): the residual gradient g = dy * mask is
-    not written by the backward apply pass; the incoming gradient dy itself is returned for `res`, the link carries the
-    mask bytes, and the graph conv's data-gradient kernel multiplies while it adds (444 MB less written per block)."""
+    lazy_res = True (only when `res` is the identity branch handed out by gcn_op.graph_conv(with_residual=True,
+    lazy_res=True), whose backward is the one consumer of its gradient): the residual gradient g = dy * mask is not
+    written by the backward apply pass; the incoming gradient dy itself is returned for `res` with the mask bytes left on
+    it (handoff 'res_mask'), and the graph conv's data-gradient kernel multiplies while it adds (444 MB less written per
+    block)."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, res, fin, relu, link=None, lazy_res=False):
@@ -197,7 +178,7 @@ class _FusedBNAct(Function):
         ctx.relu = relu
         ctx.split = math_mode.split16() and relu and x.dim() == 4
         ctx.has_res = res is not None
-        ctx.lazy_res = lazy_res if (isinstance(lazy_res, ResLink) and relu and res is not None) else None
+        ctx.lazy_res = bool(lazy_res) and relu and res is not None
         ctx.link = link if relu else None
         if ctx.link is not None:
             link.attach(x, mask, fin)
@@ -213,15 +194,13 @@ class _FusedBNAct(Function):
         dev = x.device
         lib = _lib.lib()
         link, part, ready = ctx.link, None, None
-        if link is not None:
-            if link.grad_ptr == dy.data_ptr() and link.grad_version == dy._version and (
-                    link.partials is not None or link.ready is not None):
-                # dy is the buffer the graph conv's data-gradient kernel wrote (gcn_op._GraphConv.backward), in the state
-                # it left it in: `partials` = the two sums from that kernel's epilogue (or None: reduce here, see below),
-                # `ready` = the event recorded right behind that launch
-                part, ready = link.partials, link.ready
-                link.used += 1
-            link.partials = link.grad_ptr = link.grad_version = link.ready = None
+        sums = handoff.take(dy, 'bn_sums') if link is not None else None
+        if sums is not None and sums[0] is link:
+            # dy is the gradient the graph conv's data-gradient kernel wrote (gcn_op._GraphConv.backward), in the state
+            # it left it in: `part` = the two sums from that kernel's epilogue (or None: reduce here, see below),
+            # `ready` = the event recorded right behind that launch
+            _, part, ready = sums
+            link.used += 1
         side_ok = OVERLAP_APPLY and ready is not None
 
         def reduce_pass():
@@ -239,7 +218,7 @@ class _FusedBNAct(Function):
             part_ = part if part is not None else reduce_pass()
             tot_ = bwd_finalize(part_, N * L)                 # (dbeta, dgamma, m1, m2)
             dx_ = torch.empty_like(x)
-            dres_ = torch.empty_like(x) if (ctx.has_res and ctx.lazy_res is None) else None
+            dres_ = torch.empty_like(x) if (ctx.has_res and not ctx.lazy_res) else None
             word_ = math_mode.new_word(dev) if ctx.split else None
             with torch.cuda.device(dev):
                 if word_ is not None:
@@ -276,8 +255,8 @@ class _FusedBNAct(Function):
                     t_.record_stream(main)                    # allocated from the side stream's pool, consumed here
         else:
             tot, dx, dres, word = apply_pass()
-        if ctx.lazy_res is not None:
-            ctx.lazy_res.mask, ctx.lazy_res.grad_ptr, ctx.lazy_res.grad_version = mask, dy.data_ptr(), dy._version
+        if ctx.lazy_res:
+            handoff.put(dy, 'res_mask', mask)
             dres = dy
         return dx, tot[1], tot[0], dres, None, None, None, None
 
@@ -313,10 +292,11 @@ def supported(x, bn):
     return x.is_cuda and x.dtype == torch.float32 and bn.affine and bn.track_running_stats and x.dim() >= 3
 
 
-def fused_bn_act(x, bn, res=None, relu=True, stats=None, link=None, lazy_res=None):
+def fused_bn_act(x, bn, res=None, relu=True, stats=None, link=None, lazy_res=False):
     """stats: optional kernel partials [P, C, 3 | 2] of x (see `moments`) replacing the statistics pass.
     link: a `BNLink` to hang on the result (train mode) for the graph conv that consumes it.
-    lazy_res: a `ResLink` shared with the graph conv that handed out `res`, see `_FusedBNAct` (train mode only)."""
+    lazy_res: True when the graph conv that handed out `res` takes its gradient unmasked, see `_FusedBNAct` (train mode
+    only)."""
     if bn.training:
         part = _stats_partial(x.contiguous()) if stats is None else stats
         fin = finalize(part, x.numel() // x.shape[1], bn)

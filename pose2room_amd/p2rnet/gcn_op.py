@@ -16,7 +16,7 @@ import torch
 from torch.autograd import Function
 
 from .. import _lib
-from . import bn_op, gcn_tables, math_mode
+from . import bn_op, gcn_tables, handoff, math_mode
 
 _N_BLOCKS = 256     # persistent workgroups of the reduction kernels (one per CU)
 
@@ -299,7 +299,7 @@ def _gcn3h_data_gradient(dz, sp, coef, tables, addend, addend_mask, dz_word):
 class _GraphConv(Function):
     @staticmethod
     def forward(ctx, x, weight, coef_c, coef_r, bias_cv, tables, want_stats=False, with_residual=False,
-                bn_link=None, wp_f=None, wp_b=None, lazy_res=None, split=None):
+                bn_link=None, wp_f=None, wp_b=None, lazy_res=False, split=None):
         # weight (K*64, 64): plane k rows = output channels of plane k
         dev = x.device
         t = tables.on(dev)
@@ -329,7 +329,7 @@ class _GraphConv(Function):
         ctx.wp_b = wp_b            # planes of the data gradient, already in kernel order (prepare_chain), or None
         ctx.wp_f = wp_f            # forward planes in kernel order: the adjacency-gradient kernel multiplies by them
         ctx.n_out = 2 if want_stats else 1
-        ctx.lazy_res = lazy_res if with_residual else None  # bn_op.ResLink: the identity branch's gradient arrives unmasked
+        ctx.lazy_res = bool(lazy_res) and with_residual      # the identity branch's gradient arrives unmasked
         if want_stats:
             ctx.mark_non_differentiable(out[1])
         if with_residual:
@@ -343,12 +343,12 @@ class _GraphConv(Function):
         x, W, coef_c, coef_r = ctx.saved_tensors
         dres = rest[ctx.n_out - 1] if len(rest) >= ctx.n_out else None     # gradient of the identity branch, if any
         dres_mask = None
-        if ctx.lazy_res is not None and dres is not None:
+        if ctx.lazy_res and dres is not None:
             dres = dres.contiguous()
-            dres_mask = ctx.lazy_res.take(dres)
+            dres_mask = handoff.take(dres, 'res_mask')
             if dres_mask is None:
                 raise RuntimeError("graph_conv: the identity branch's gradient was announced unmasked (lazy_res) but no "
-                                   "mask is registered for it -- the residual has another consumer than this op")
+                                   "mask came with it -- the residual has another consumer than this op")
         tables = ctx.tables
         dev = x.device
         t = tables.on(dev)
@@ -360,24 +360,18 @@ class _GraphConv(Function):
         dz_word = math_mode.range_word(dz) if ctx.split is not None else None
         if ctx.needs_input_grad[0]:
             # dX = sum_k W_k^T (dZ . A_k^T): forward kernel with transposed planes + row lists
+            link, sums = ctx.bn_link, None
+            use_link = (link is not None and link.intact() and link.u.shape == x.shape
+                        and (ctx.split is not None or tables.gen2))
             if ctx.split is not None:
-                link = ctx.bn_link
-                use_link = link is not None and link.intact() and link.u.shape == x.shape
                 # (the sums epilogue of the exact kernel does not exist here: the BatchNorm backward in front runs its
                 # own reduction pass -- on the side stream under the gradient kernels below when the overlap is on)
                 ad = dres.contiguous() if dres is not None else None
                 if dres_mask is not None and dres_mask.data_ptr() % 4 != 0:
                     ad, dres_mask = ad * (dres_mask != 0), None
                 dx = _gcn3h_data_gradient(dz, ctx.split[1], coef_r.contiguous(), tables, ad, dres_mask, dz_word)
-                if use_link:
-                    link.partials = None
-                    link.grad_ptr, link.grad_version = dx.data_ptr(), dx._version
-                    link.ready = torch.cuda.Event()
-                    link.ready.record(torch.cuda.current_stream(dev))
                 dres = None
             elif tables.gen2:
-                link = ctx.bn_link
-                use_link = link is not None and link.intact() and link.u.shape == x.shape
                 # the sums either leave through this kernel's epilogue, or -- when the BatchNorm backward will run its
                 # passes on a side stream under the gradient kernels launched below -- are left to its own reduction pass
                 # (HBM-bound, hidden there, while the epilogue form costs 0.18 ms of this kernel with the matrix pipe idle)
@@ -388,24 +382,22 @@ class _GraphConv(Function):
                                    t['stream_r'], None, tables, addend=dres.contiguous() if dres is not None else None,
                                    want_stats=emit, bwd=(link.u, link.mask, link.fin) if emit else None,
                                    form=1, addend_mask=dres_mask)
-                if use_link:
-                    # dx is the whole gradient of the previous block's output: its BatchNorm backward takes the
-                    # two per-channel sums from here instead of a pass over dx and its saved input
-                    if emit:
-                        dx, link.partials = dx
-                    else:
-                        link.partials = None
-                    link.grad_ptr, link.grad_version = dx.data_ptr(), dx._version
-                    # dx and the sums are complete HERE; the weight- and adjacency-gradient launches below do not
-                    # touch them (bn_op._FusedBNAct.backward runs its apply pass under them, on a side stream)
-                    link.ready = torch.cuda.Event()
-                    link.ready.record(torch.cuda.current_stream(dev))
+                if emit:
+                    dx, sums = dx
                 dres = None
             else:
                 if dres_mask is not None:
                     dres, dres_mask = dres * (dres_mask != 0), None
                 Wt = W.view(K, C, C).transpose(1, 2).contiguous()            # [k][ci][c]
                 dx = _gcn_forward(dz, Wt, t['nbr_r'], coef_r.contiguous(), tables.LkA_r, None, tables)
+            if use_link:
+                # dx is the whole gradient of the previous block's output: its BatchNorm backward takes the two
+                # per-channel sums from here (or None: its own reduction pass) instead of a pass over dx and its saved
+                # input.  dx and the sums are complete HERE; the weight- and adjacency-gradient launches below do not
+                # touch them (bn_op._FusedBNAct.backward runs its apply pass under them, on a side stream)
+                ready = torch.cuda.Event()
+                ready.record(torch.cuda.current_stream(dev))
+                handoff.put(dx, 'bn_sums', (link, sums, ready))
         lib = _lib.lib()
         st = _lib.current_stream(dev)
         with torch.cuda.device(dev):
@@ -509,7 +501,7 @@ def supported(x, weight, A):
 
 
 def graph_conv(x, weight, bias, Aeff, tables, want_stats=False, with_residual=False, bn_link=None, prepared=None,
-               lazy_res=None):
+               lazy_res=False):
     """x (N,64,T,V); weight (K*64,64[,1,1]); bias (K*64) or None; Aeff (K,V,V).
     with_residual: additionally return x itself (last output) for the caller's identity branch; its gradient is then
     added inside the data-gradient kernel.
@@ -520,8 +512,8 @@ def graph_conv(x, weight, bias, Aeff, tables, want_stats=False, with_residual=Fa
     reduction pass of that BatchNorm's backward.
     prepared: this block's `BlockParams` from `prepare_chain` (coefficient tables, bias table and kernel-order
     planes computed for all blocks at once); Aeff is then not looked at.
-    lazy_res (with_residual): a `bn_op.ResLink` shared with the `bn_op.fused_bn_act(..., lazy_res=link)` the identity
-    branch goes into, whose backward hands its gradient over unmasked; this op's data-gradient kernel applies the mask
+    lazy_res (with_residual): True when the identity branch goes into a `bn_op.fused_bn_act(..., lazy_res=True)`, whose
+    backward hands its gradient over unmasked with the mask bytes on it; this op's data-gradient kernel applies the mask
     while it adds."""
     K, V = tables.K, tables.V
     t = tables.on(x.device)
@@ -584,7 +576,6 @@ def prepare_chain(blocks, A, importances, tables, frames=None):
         split = (math_mode.split16() and tables.gen3h and V == 53 and frames is not None and frames % 16 == 0)
         if split:
             from . import tconv_op
-            math_mode.reset()
             # one (scale, three fp16 planes) per weight tensor, then one gather per operand layout: a dozen launches
             gsf, gsf_inv = split_planes(W, tables.pairs_c)
             gsb, gsb_inv = split_planes(W, tables.pairs_r, transposed=True)

@@ -12,17 +12,17 @@ The mode is read when an op runs (forward), and the backward of an op follows th
 
 Range words.  A split16 kernel that takes a runtime tensor as an MFMA operand (the incoming gradients; the block
 inputs of the graph conv) needs max |x| of that tensor to place it in fp16's range.  The kernel that WROTE the tensor
-leaves that maximum as one uint32 in device memory (`announce`); the consumer picks it up by the tensor's identity
-(`range_word`), or computes it with one extra read of the tensor when nobody announced it.
+leaves that maximum as one uint32 in device memory on the tensor itself (`announce`, see handoff); the consumer picks it
+up there (`range_word`), or computes it with one extra read of the tensor when nobody announced it.
 """
 import contextlib
 import ctypes
 import os
-from collections import OrderedDict
 
 import torch
 
 from .. import _lib
+from . import handoff
 
 MODES = ('exact', 'split16')
 _mode = os.environ.get('P2R_MATH', 'exact') or 'exact'
@@ -56,8 +56,6 @@ def use(m):
 
 
 # ---- range words ------------------------------------------------------------------------------------------------------
-_WORDS = OrderedDict()      # data_ptr -> (version counter, numel, word tensor); bounded, cleared per forward pass
-_MAX_WORDS = 64
 FALLBACK_PASSES = 0         # how many range words had to be computed by a separate pass (tests, profiling)
 
 
@@ -67,18 +65,16 @@ def new_word(device):
 
 def announce(t, word):
     """`word` (int32[1], device) holds the float bits of max |t| -- written by the kernel that produced `t`."""
-    _WORDS[t.data_ptr()] = (t._version, t.numel(), word)
-    while len(_WORDS) > _MAX_WORDS:
-        _WORDS.popitem(last=False)
+    handoff.put(t, 'range_word', word)
 
 
 def range_word(t, keep=False):
-    """The range word of `t`: the announced one when `t` is the very tensor (address, version, size) its producer
-    announced, otherwise one pass over `t` (p2r_absmax_bits)."""
+    """The range word of `t`: the one announced for `t` (consumed unless `keep`), otherwise one pass over `t`
+    (p2r_absmax_bits)."""
     global FALLBACK_PASSES
-    e = _WORDS.get(t.data_ptr()) if keep else _WORDS.pop(t.data_ptr(), None)
-    if e is not None and e[0] == t._version and e[1] == t.numel() and e[2].device == t.device:
-        return e[2]
+    word = handoff.peek(t, 'range_word') if keep else handoff.take(t, 'range_word')
+    if word is not None:
+        return word
     word = new_word(t.device)
     with torch.cuda.device(t.device):
         _lib.check(_lib.lib().p2r_absmax_bits(ctypes.c_longlong(t.numel()), _lib.ptr(t), _lib.ptr(word),
@@ -88,7 +84,7 @@ def range_word(t, keep=False):
 
 
 def reset():
-    _WORDS.clear()
+    """Nothing to clear: announced words live on their tensors (kept so that callers between runs need not change)."""
 
 
 # ---- weights: power-of-two scale and the two fp16 parts (device arithmetic only, no host round trip) --------------------

@@ -26,7 +26,6 @@ def run(device, batch=2, frames=128):
         out16 = one_step()
     finally:
         math_mode.set_mode('exact')
-        math_mode.reset()
     for k in ('total', 'vote_loss', 'center_loss', 'size_loss', 'heading_loss', 'sem_cls_loss', 'objectness_loss'):
         assert abs(out16[k] - out[k]) <= 1e-3 * max(1.0, abs(out[k])), (k, out[k], out16[k])
     return out

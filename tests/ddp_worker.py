@@ -118,7 +118,6 @@ def main():
                     differ = [n for n in base if not torch.equal(base[n], got[n])]
                     worst = max([((base[n] - got[n]).abs().max() / (base[n].abs().max() + 1e-30)).item() for n in differ] or [0.0])
                     report.append((mode, rnd, 'main' if inline else 'side', len(differ), worst, differ[:3]))
-        math_mode.reset()
     assert all(r[3] == 0 for r in report), f'reduced gradients differ from the one-stream order: {report}'
     if rank == 0:
         print(json.dumps({'world': world, 'side_stream_equals_one_stream': True, 'modes': ['exact', 'split16'],

@@ -210,7 +210,7 @@ def test_side_stream_bn_backward_apply_is_the_same_pass(dev):
 
 def test_lazy_residual_gradient_is_the_masked_one(dev):
     """The residual-branch gradient of an st_gcn_block is handed to the graph-conv data gradient unmasked (+ the ReLU mask
-    bytes, bn_op.ResLink) and multiplied there: the same additions of the same values as when the BatchNorm-backward pass
+    bytes, left on that gradient) and multiplied there: the same additions of the same values as when the BatchNorm-backward pass
     writes dout * mask.  The six blocks are fed a fixed activation (the embedding in front of them merges its statistics
     with LDS float atomics: two runs of the whole backbone differ by a flipped borderline ReLU now and then, 5e-3 of a
     gradient), so that the forward pass of both runs is the same bit for bit and the two hand-overs can be held to

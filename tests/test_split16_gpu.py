@@ -53,7 +53,26 @@ def test_range_word_announced_only_for_the_very_tensor(dev):
     math_mode.announce(x, w)
     x.add_(1.0)                                                          # another version of the buffer
     assert math_mode.range_word(x) is not w
-    math_mode.reset()
+
+
+def test_range_word_is_not_inherited_through_reused_memory(dev):
+    """A word announced for a tensor nobody consumed must not pass to a new tensor the caching allocator places in the
+    same block: same shape, same version, other values.  A stale word that is too small sends the split operands to fp16
+    inf; one that is too large silently costs precision."""
+    from pose2room_amd.p2rnet import math_mode
+    shape = (2, 64, 32, 53)
+    x = torch.randn(shape, device=dev)
+    w = math_mode.new_word(dev)
+    w.view(torch.float32).fill_(1.0)                                     # deliberately wrong: max |x| is about 4.5
+    math_mode.announce(x, w)
+    ptr, version = x.data_ptr(), x._version
+    del x
+    y = torch.randn(shape, device=dev)
+    print('same block reused:', y.data_ptr() == ptr and y._version == version)
+    before = math_mode.FALLBACK_PASSES
+    word = math_mode.range_word(y)
+    assert math_mode.FALLBACK_PASSES == before + 1
+    assert word.view(torch.float32).item() == y.abs().max().item()
 
 
 def _tconv_inputs(N, T, seed, gmag=None):
@@ -217,7 +236,6 @@ def test_bn_relu_tconv_module_in_split16_mode(dev, N, T):
             a, b, r = a * decided, b * decided, r * decided
         es, ee = _rel(a, r), _rel(b, r)
         assert es <= 1.5 * ee + 1e-6, (what, es, ee)
-    math_mode.reset()
 
 
 # ---- graph conv ---------------------------------------------------------------------------------------------------------
@@ -267,7 +285,6 @@ def test_graph_conv_split16_vs_float64_and_exact(dev, N, T, gmag):
         es, ee = _rel(res['split16'][i], want[i]), _rel(res['exact'][i], want[i])
         assert es <= 1.5 * ee + FLOOR, (what, gmag, es, ee)
     assert not torch.equal(res['split16'][0], res['exact'][0])          # the split kernels did run
-    math_mode.reset()
 
 
 def test_graph_conv_split16_masked_addend_and_statistics(dev):
@@ -319,7 +336,6 @@ def test_graph_conv_split16_aggregate_headroom(dev):
         ze = gcn_op.graph_conv(x.to(dev), w.to(dev), b.to(dev), (At * imp).to(dev), tables)
     assert torch.isfinite(z).all()
     assert _rel(z, zr) <= 1.5 * _rel(ze, zr) + FLOOR
-    math_mode.reset()
 
 
 @pytest.mark.parametrize("N,T", [(2, 80), (3, 1008)])
@@ -421,7 +437,6 @@ def test_split16_mode_falls_back_to_the_exact_kernels(dev, N, T):
     assert torch.equal(res['exact'][0], res['split16'][0]) and torch.equal(res['exact'][1], res['split16'][1])   # forward: deterministic kernels
     for a, b_ in zip(res['exact'], res['split16']):
         assert _rel(a, b_.double()) <= 1e-5
-    math_mode.reset()
 
 
 def test_split16_mode_other_skeletons_run_exact(dev):
@@ -444,7 +459,6 @@ def test_split16_mode_other_skeletons_run_exact(dev):
         with math_mode.use(m):
             out[m] = gcn_op.graph_conv(x, w, None, torch.tensor(A).to(dev), tables)
     assert torch.equal(out['exact'], out['split16'])
-    math_mode.reset()
 
 
 @pytest.mark.parametrize("N,T", [(1, 16), (3, 48), (2, 256)])
@@ -539,4 +553,3 @@ def test_split16_kernels_write_only_their_outputs(dev, N, T):
                                                 _lib.ptr(uw), st), "tconvh data gradient")
         check("tconvh data gradient", gb, gout)
         check("tconvh data gradient sums", s2b, s2)
-    math_mode.reset()

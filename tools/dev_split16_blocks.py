@@ -32,7 +32,6 @@ for m in ('exact', 'split16'):
         ep = net(data)
         loss = net.loss(ep, data)
         loss['total'].backward()
-    math_mode.reset()
     cap['grads'] = {n: p.grad.detach().clone() for n, p in net.named_parameters() if p.grad is not None}
     res[m] = cap
 for k in sorted(k for k in res['exact'] if k != 'grads'):

@@ -30,7 +30,6 @@ for m in ('exact', 'split16'):
         blk.register_forward_hook(fb)
     with math_mode.use(m):
         run_g4e(net, make_batch(2, 256, seed=356, device=dev), z, dev, contextlib.nullcontext, tol=1.0)
-    math_mode.reset()
     c['gb2'] = dict(net.named_parameters())['backbone.st_gcn_networks.2.gcn.conv.bias'].grad.clone()
 for i in range(6):
     a, b = cap['exact'], cap['split16']

@@ -20,7 +20,6 @@ for which in ('g4e', 'g4b'):
                 res[m] = run_g4e(net, make_batch(2, 256, seed=356, device=dev), z, dev, contextlib.nullcontext, tol=1.0)
             else:
                 res[m] = run_g4b(net, make_batch(2, 256, seed=356, device=dev), z, dev, contextlib.nullcontext, tol=1.0)
-        math_mode.reset()
     names = sorted(res['split16'], key=lambda n: -res['split16'][n])[:12]
     print(which, 'worst (split16 | exact):')
     for n in names:
