@@ -624,6 +624,41 @@ typedef struct p2r_mdn_sample_head {
 int p2r_mdn_sample(int nheads, const p2r_mdn_sample_head *heads, int B, int G, int L, int pi_ctot, int H,
                    const int *n_samples, unsigned long long seed, int h_offset, void *stream);
 
+/* Batch assembly from a device-resident sample store (csrc/batch_assemble.hip; the reference's dataloader.py:31-161,
+ * `augment_data` + `__getitem__` + `collate_fn`, for one batch in one launch).  Store (all device memory, N samples,
+ * F frames in all, J joints, K box slots):
+ *   joints (F, J, 3) f32, votes (F, J, 10) f32 -- the samples' raw frames back to back (column 0 of a vote row = vote
+ *   mask, 1..9 = three 3-vectors); frame_offset (N) i64 first frame of each sample; n_frames (N) i32 its T0, 1..65535;
+ *   floor_height (N, 2) f64: the use_height floor of the augmented sample (f64 percentile) and of the plain one (an f32
+ *   value); box tables with V = 9 variants, v = 4 flip + angle index (-pi, -pi/2, 0, pi/2) and v = 8 = no augmentation:
+ *   box_center (N, V, K, 3) f64 before the offset, box_heading (N, V, K, 2) f32 (sin, cos), box_size (N, K, 3) f32 (log
+ *   size), box_mask (N, K) f32, box_cls (N, K) i64.
+ * Per batch sample b (device arrays): sel (B, 3) i64 = (sample id, flip, variant); aug (B, 10) f64 = the nine entries
+ * of rot_y(theta) row-major as the host computes them, then the x-z offset (aug may be NULL when augment == 0).
+ * Outputs: the collate_fn contract, input_joints (B, T, J, 3 + use_height) f32, vote_label (B, T, J, 9) f32,
+ * vote_label_mask (B, T, J) i64, center_label / size (B, K, 3) f32, heading (B, K, 2) f32, box_label_mask (B, K) f32,
+ * sem_cls_label (B, K) i64, with T = num_frames.  Ids outside 0..N-1 are the caller's to reject: the kernel writes
+ * nothing for them.  Every other output element is written. */
+typedef struct p2r_sample_store {
+  const float *joints, *votes;
+  const long long *frame_offset;
+  const int *n_frames;
+  const double *floor_height, *box_center;
+  const float *box_heading, *box_size, *box_mask;
+  const long long *box_cls;
+  long long n_frames_total;
+  int n_samples, J, K;
+} p2r_sample_store;
+typedef struct p2r_batch_out {
+  float *input_joints, *vote_label;
+  long long *vote_label_mask;
+  float *center_label, *size, *heading, *box_label_mask;
+  long long *sem_cls_label;
+} p2r_batch_out;
+#define P2R_BOX_VARIANTS 9
+int p2r_assemble_batch(const p2r_sample_store *store, int B, const long long *sel, const double *aug, int augment,
+                       int use_height, int num_frames, const p2r_batch_out *out, void *stream);
+
 /* ---- seams of the ST-GCN backbone (csrc/seed_ops.hip) ------------------------------------------------------------ */
 
 /* frame gather in front of conv_joint (stgcn.py:142-149; conv_joint is pointwise in time, so the gather may come

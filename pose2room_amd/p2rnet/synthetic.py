@@ -84,3 +84,37 @@ def make_batch(batch_size, num_frames, seed=1234, rank=0, device=None):
     if device is not None:
         batch = {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in batch.items()}
     return batch
+
+
+def make_raw_sample(num_frames, n_boxes=6, seed=0, name=None):
+    """One seeded raw sample in the on-disk layout `dataloader.read_sample_hdf5` returns -- joints (T0,53,3) f32, votes
+    (T0,53,10) f32 (column 0 = vote mask, 1..9 = offsets to up to three object centres), instance list with class_id,
+    centroid, R_mat (a rotation about y) and size in f64 -- plus a name.  Input of the device sample store's tests and
+    of tools/loader_throughput.py.  A few joints sit at y = -0.0 (flip / rotation must keep their sign)."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    T0 = num_frames
+    tmpl = skeleton_template().numpy().astype(np.float64)
+    hip = np.cumsum(rng.normal(0.0, 0.05, (T0, 3)), 0).clip(-3.0, 3.0)
+    hip[:, 1] = 0.9
+    joints = (hip[:, None, :] + tmpl[None] + rng.normal(0.0, 0.02, (T0, N_JOINTS, 3))).astype(np.float32)
+    joints[rng.random((T0, N_JOINTS)) < 0.01, 1] = -0.0
+    instances, centres = [], []
+    for k in range(n_boxes):
+        th = rng.choice([0.0, 0.5 * np.pi, np.pi, -0.5 * np.pi]) + rng.normal(0.0, 0.3)
+        R = np.array([[np.cos(th), 0., -np.sin(th)], [0., 1., 0.], [np.sin(th), 0., np.cos(th)]])
+        c = np.array([rng.uniform(-3, 3), rng.uniform(0.2, 1.5), rng.uniform(-3, 3)])
+        instances.append({'class_id': int(rng.integers(0, N_CLASS)), 'centroid': c, 'R_mat': R,
+                          'size': rng.uniform(0.3, 2.0, 3)})
+        centres.append(c)
+    votes = np.zeros((T0, N_JOINTS, 10), np.float32)
+    if n_boxes:
+        centres = np.array(centres)
+        d = np.linalg.norm(joints[:, :, None, :] - centres[None, None], axis=-1)       # (T0, 53, n)
+        near = np.argsort(d, -1)[..., :3]
+        hit = np.take_along_axis(d, near[..., :1], -1)[..., 0] < 1.5 * CONTACT_DIST
+        votes[..., 0] = hit
+        for i in range(3):
+            votes[..., 1 + 3 * i:4 + 3 * i] = np.where(hit[..., None], centres[near[..., min(i, n_boxes - 1)]] - joints,
+                                                       0.0)
+    return joints, votes, instances, name if name is not None else f'synthetic_{seed}'
