@@ -49,6 +49,20 @@ static inline hipError_t p2r_allow_big_lds(K kernel, unsigned char (&done)[P2R_M
   return e;
 }
 
+// Launch of a kernel with up to 160 KB of dynamic LDS: the attribute is set on first use per device, launch errors come
+// back as the C-ABI's int.  The per-device flags belong to the instantiation <KERNEL, Args...>: call sites that pass
+// the same kernel with other argument types (nullptr for a pointer) have flags of their own and set the attribute once
+// more, which is harmless.
+template <auto KERNEL, typename... Args>
+static inline int p2r_launch_big_lds(int blocks, int threads, size_t lds, void *stream, Args... args) {
+  static unsigned char lds_ok[P2R_MAX_DEVICES];
+  hipError_t e = p2r_allow_big_lds(KERNEL, lds_ok);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(KERNEL, dim3(blocks), dim3(threads), lds, p2r_stream(stream), args...);
+  P2R_LAUNCH_CHECK();
+  return P2R_OK;
+}
+
 // Squared distance exactly as the reference writes it:
 // (a-b)*(a-b) + (c-d)*(c-d) + (e-f)*(e-f), left-to-right, no contraction.
 __device__ __forceinline__ float p2r_sqdist(float ax, float ay, float az,

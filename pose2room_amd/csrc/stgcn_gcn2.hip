@@ -16,7 +16,7 @@
 //     lane group of a 32-lane LDS pass on the other 16 banks.
 //   * The 64 input channels are processed in four phases of 16 (one MFMA k-step group per phase and
 //     m-tile), each phase's 16 x 848 slice of the X tile living in one of two 53 KB LDS buffers.  The
-//     slices are copied by LDS-DMA (global_load_lds_dwordx4: no VGPRs, no ds_write pass) in the global
+//     slices are copied by LDS-DMA (tile_dma16 of stgcn_tile.h: no VGPRs, no ds_write pass) in the global
 //     order [channel][frame][joint], one 1 KB piece per wave and plane iteration, so the copy of phase
 //     p+1 is spread under the MFMAs of phase p and a wave never waits for a piece it has just issued.
 //   * Persistent workgroups (one per CU) walk the tiles; accumulators (64 rows x 16 frames per joint,
@@ -27,17 +27,13 @@
 //
 // Bit-level behaviour: every output element is the same fmaf / MFMA chain for a given column
 // whatever the tile shape; run-to-run deterministic (no atomics).
-#include "p2r_common.h"
+#include "stgcn_tile.h"
 
 #include <type_traits>
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int G2_F = 16;            // frames per tile = columns of an MFMA n-tile
-constexpr int G2_CP = 16;           // channels per phase
-constexpr int G2_NPH = 4;           // phases (64 channels)
+constexpr int G2_F = TILE_F, G2_CP = TILE_CP, G2_NPH = TILE_NPH;     // the shared tile (stgcn_tile.h)
 
 struct G2Params {
   int T, V, K;
@@ -45,26 +41,6 @@ struct G2Params {
   int ltot;                         // rows of the (nbr, coef) tables = sum of the per-plane list lengths
   int vec;                          // 1: rows are 16-byte aligned and T*V % 4 == 0 -> 16-byte DMA pieces
 };
-
-// LDS-DMA pieces as inline assembly: with the builtin, hipcc treats every later LDS read as possibly aliasing the
-// copy in flight and puts `s_waitcnt vmcnt(0)` in front of it -- which here would stall every record fetch on the
-// piece (and the A-operand prefetch) just issued.  The copies land in the buffer nobody reads during the current
-// phase; the issuing wave waits for them (vmcnt(0)) right before the phase barrier.  M0 = LDS destination of lane 0.
-__device__ __forceinline__ unsigned g2_lds_addr(const float *p) {
-  return (unsigned)(size_t)(const __attribute__((address_space(3))) float *)p;
-}
-__device__ __forceinline__ void g2_dma16(const float *src, float *lds_dst) {
-  unsigned keep;
-  const unsigned dst = __builtin_amdgcn_readfirstlane(g2_lds_addr(lds_dst));
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
-}
-__device__ __forceinline__ void g2_dma4(const float *src, float *lds_dst) {
-  unsigned keep;
-  const unsigned dst = __builtin_amdgcn_readfirstlane(g2_lds_addr(lds_dst));
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
-}
 
 // Work stream of a wave (global memory, written by gcn2_fill_stream_kernel from the caller's template and the current
 // coefficients right before the main kernel): one 48-byte record per pass,
@@ -145,8 +121,9 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void gcn2_kernel(
 
   // ---- LDS-DMA of one phase slice (16 channel rows x frames*V floats), split into per-wave pieces ----------
   constexpr int NV4 = BUF / 4;                        // float4 elements per slice
-  constexpr int PIECES16 = (NV4 + 63) / 64;           // wave instructions per slice (53 for V = 53)
-  constexpr int PW16 = (PIECES16 + NW - 1) / NW;      // per wave
+  constexpr int PIECES16 = tile_pieces(NV4);          // wave instructions per slice (53 for V = 53)
+  constexpr int PW16 = tile_pw(NV4);                  // per wave
+  static_assert(NW == TILE_NW, "pieces are dealt to the tile's waves");
   constexpr int PIECES4 = (BUF + 63) / 64;
   constexpr int PW4 = (PIECES4 + NW - 1) / NW;
   auto dma_piece = [&](int piece_i, float *buf, const float *xrow0, int valid_cols) {
@@ -156,7 +133,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void gcn2_kernel(
       if (piece_i < PW16 && pc < PIECES16) {
         const int e = pc * 64 + lane;                 // float4 index in the slice
         const int row = e / (RS / 4), c4 = e - row * (RS / 4);
-        if (e < NV4) g2_dma16(xrow0 + (size_t)row * row_stride + 4 * c4, buf + pc * 256);
+        if (e < NV4) tile_dma16(xrow0 + (size_t)row * row_stride + 4 * c4, buf + pc * 256);
       }
     } else {
       // tail tiles / unaligned rows: 4-byte pieces, several per call
@@ -168,7 +145,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void gcn2_kernel(
         if (pi < PW4 && pc < PIECES4) {
           const int e = pc * 64 + lane;
           const int row = e / RS, col = e - row * RS;
-          if (e < BUF && col < valid_cols) g2_dma4(xrow0 + (size_t)row * row_stride + col, buf + pc * 64);
+          if (e < BUF && col < valid_cols) tile_dma4(xrow0 + (size_t)row * row_stride + col, buf + pc * 64);
         }
       }
     }
@@ -176,14 +153,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void gcn2_kernel(
 
   f32x4 acc[SLOTS][4];
   float a_nxt[4][4];                                  // A operands of the next (plane, phase): W'[k][ph][m][lane][s]
-  auto load_a = [&](int k, int ph) {
-    const float4 *wp = reinterpret_cast<const float4 *>(Wp) + ((size_t)(k * G2_NPH + ph) * 4) * 64 + lane;
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      const float4 u = wp[m * 64];
-      a_nxt[m][0] = u.x; a_nxt[m][1] = u.y; a_nxt[m][2] = u.z; a_nxt[m][3] = u.w;
-    }
-  };
+  auto load_a = [&](int k, int ph) { tile_load_a(a_nxt, Wp, k, ph, lane); };
 
   // gathers of one record: xv[j][s] = X[row 4 s + g][frame r, joint j-th source], first NE entries
   auto gather = [&](auto ne, const int4 &e0, const char *xl, float (&xv)[6][4]) {
@@ -498,16 +468,11 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void gcn2_kernel(
 
   if (stats_partial) {
     __syncthreads();
-    if (tid < 128) {
-      float t = 0.f;
-#pragma unroll
-      for (int w = 0; w < NW; ++w) t += rowstat[w * 128 + tid];
-      stats_partial[(size_t)blockIdx.x * 128 + tid] = t;
-    }
+    tile_write_sums<2>(rowstat, stats_partial, tid);
   }
 }
 
-constexpr int G2_NW = 8, G2_SLOTS = 7;
+constexpr int G2_NW = TILE_NW, G2_SLOTS = TILE_SLOTS;
 constexpr int G2_LAYOUT = 0;          // LDS position of (frame, joint) inside a row: the tensor's own [frame][joint] order
 
 }  // namespace
@@ -558,21 +523,11 @@ extern "C" int p2r_stgcn_gcn2_forward(int N, int T, int V, int K, int ltot, cons
   hipLaunchKernelGGL(gcn2_fill_stream_kernel, dim3((n_stream + 255) / 256), dim3(256), 0, p2r_stream(stream_h), n_stream,
                      stream, coef, stream_work);
   P2R_LAUNCH_CHECK();
-  if (bwd) {
-    auto kern = gcn2_kernel<G2_NW, G2_SLOTS, 53, G2_LAYOUT, true>;
-    static unsigned char lds_ok[P2R_MAX_DEVICES];
-    hipError_t e = p2r_allow_big_lds(kern, lds_ok);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(G2_NW * 64), lds, p2r_stream(stream_h), p, x, Wp, stream_work, bias_cv,
-                       addend, z, stats_partial, bwd_u, bwd_mask, bwd_fin);
-  } else {
-    auto kern = gcn2_kernel<G2_NW, G2_SLOTS, 53, G2_LAYOUT, false>;
-    static unsigned char lds_ok[P2R_MAX_DEVICES];
-    hipError_t e = p2r_allow_big_lds(kern, lds_ok);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(G2_NW * 64), lds, p2r_stream(stream_h), p, x, Wp, stream_work, bias_cv,
-                       addend, z, stats_partial, nullptr, nullptr, nullptr);
-  }
-  P2R_LAUNCH_CHECK();
-  return P2R_OK;
+  if (bwd)
+    return p2r_launch_big_lds<gcn2_kernel<G2_NW, G2_SLOTS, 53, G2_LAYOUT, true>>(
+        blocks, G2_NW * 64, lds, stream_h, p, x, Wp, stream_work, bias_cv, addend, z, stats_partial, bwd_u, bwd_mask,
+        bwd_fin);
+  return p2r_launch_big_lds<gcn2_kernel<G2_NW, G2_SLOTS, 53, G2_LAYOUT, false>>(
+      blocks, G2_NW * 64, lds, stream_h, p, x, Wp, stream_work, bias_cv, addend, z, stats_partial, nullptr, nullptr,
+      nullptr);
 }

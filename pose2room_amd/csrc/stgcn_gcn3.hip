@@ -22,7 +22,7 @@
 //
 // The host only launches this kernel for tables whose pattern_signature equals the generated one
 // (p2r_stgcn_gcn3_signature); every other adjacency runs on gcn2 / the first-generation kernel.
-#include "p2r_common.h"
+#include "stgcn_tile.h"
 
 #include "gcn3_sched.inc"
 
@@ -40,19 +40,10 @@ extern "C" int p2r_debug_g3_trace(unsigned long long *dst) {
 #endif
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int G3_F = 16;             // frames per tile = columns of an MFMA n-tile
-constexpr int G3_CP = 16;            // channels per phase
-constexpr int G3_NPH = 4;            // phases (64 channels)
-constexpr int G3_NW = 8;
-constexpr int G3_SLOTS = 7;
-constexpr int G3_RS = G3_F * G3_V;   // LDS row stride (floats): 848 == 16 (mod 32)
-constexpr int G3_BUF = G3_CP * G3_RS;
-constexpr int G3_NV4 = G3_BUF / 4;                     // float4 elements per slice: 3392 = 53 pieces of 64
-constexpr int G3_PIECES = (G3_NV4 + 63) / 64;          // 53
-constexpr int G3_PW = (G3_PIECES + G3_NW - 1) / G3_NW; // 7 per wave
-static_assert(G3_V == 53 && G3_K == 11, "schedule generated for another skeleton");
+// the shared tile (stgcn_tile.h) under the names the generated schedule and this file use
+constexpr int G3_F = TILE_F, G3_CP = TILE_CP, G3_NPH = TILE_NPH, G3_NW = TILE_NW, G3_SLOTS = TILE_SLOTS;
+constexpr int G3_RS = TILE_RS, G3_BUF = TILE_BUF, G3_NV4 = TILE_NV4, G3_PW = TILE_PW;
+static_assert(G3_V == TILE_V && G3_K == 11, "schedule generated for another skeleton");
 
 struct G3Params {
   int T;
@@ -72,18 +63,6 @@ constexpr int g3_wave_joints(int form, int w) {                            // jo
   return n;
 }
 constexpr int G3_ST = 3;   // floats per (wave, row) statistics entry: (sum, sum of squares) about the pivot, pivot
-
-__device__ __forceinline__ unsigned g3_lds_addr(const float *p) {
-  return (unsigned)(size_t)(const __attribute__((address_space(3))) float *)p;
-}
-// one 1 KB LDS-DMA piece: lane's 16 bytes at (uniform base + per-lane byte offset) -> LDS dst + 16 * lane.  Inline
-// assembly for the reason given in stgcn_gcn2.hip (no vmcnt(0) in front of later LDS reads); M0 = LDS destination.
-__device__ __forceinline__ void g3_dma16(const float *base, int voff, float *lds_dst) {
-  unsigned keep;
-  const unsigned dst = __builtin_amdgcn_readfirstlane(g3_lds_addr(lds_dst));
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(base), "s"(dst) : "memory");
-}
 
 // xv[j][s] = X[row 4 s + g][frame r, joint of entry j]: ds_read with immediate offsets off the lane's base
 template <int NE, int O0, int O1, int O2, int O3, int O4, int O5>
@@ -183,7 +162,7 @@ __device__ __forceinline__ void g3_mfma16(f32x4 (&acc)[4], const float (&a)[4][4
 // merge with copies and scratch traffic.  Barriers are counted by the hardware, not matched by address, so the waves
 // of a workgroup may meet at different program counters.
 // BWD (data-gradient launches): the statistics epilogue emits the reduction pass of the BatchNorm + residual + ReLU
-// backward of the block in front, exactly as gcn2_kernel<.., true> does (see stgcn_gcn2.hip).
+// backward of the block in front, exactly as gcn2_kernel<.., true> does (stgcn_gcn2.hip keeps the plain-code statement).
 // MADD (BWD launches): the addend is masked on the way in -- addend * (addend_mask != 0) -- i.e. the residual-branch
 // gradient g = dout * relu_mask of the block is formed here from the incoming gradient and the mask bytes instead of
 // being written (444 MB at bs=32, T=1024) by the BatchNorm-backward pass and read back.
@@ -222,20 +201,13 @@ __device__ __forceinline__ void g3_wave_main(
     const int pc = i * NW + wave;
     const int e = pc * 64 + lane;
     const int row = e / (RS / 4), c4 = e - row * (RS / 4);
-    doff[i] = (pc < G3_PIECES && e < G3_NV4) ? (int)(((size_t)row * row_stride + 4 * c4) * sizeof(float)) : -1;
+    doff[i] = (pc < TILE_PIECES && e < G3_NV4) ? (int)(((size_t)row * row_stride + 4 * c4) * sizeof(float)) : -1;
   }
 
   f32x4 acc[SLOTS][4];
   float aS[2][4][4];                                  // two A-operand sets: W'[k][ph][m][lane][s]
   float b_cur[4];
-  auto load_a = [&](float (&a)[4][4], int k, int ph) {
-    const float4 *wp = reinterpret_cast<const float4 *>(Wp) + ((size_t)(k * G3_NPH + ph) * 4) * 64 + lane;
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      const float4 u = wp[m * 64];
-      a[m][0] = u.x; a[m][1] = u.y; a[m][2] = u.z; a[m][3] = u.w;
-    }
-  };
+  auto load_a = [&](float (&a)[4][4], int k, int ph) { tile_load_a(a, Wp, k, ph, lane); };
 
   int tile = blockIdx.x;
   // prologue: phase 0 of the first tile, all pieces at once; A operands of the wave's first plane
@@ -244,7 +216,7 @@ __device__ __forceinline__ void g3_wave_main(
     const float *xr = x + (size_t)seq * 64 * row_stride + (size_t)t0 * V;
 #pragma unroll
     for (int i = 0; i < G3_PW; ++i)
-      if (doff[i] >= 0) g3_dma16(xr, doff[i], lds + (i * NW + wave) * 256);
+      if (doff[i] >= 0) tile_dma16(xr, doff[i], lds + (i * NW + wave) * 256);
   }
   load_a(aS[0], g3_plane0[FORM][WAVE], 0);
 
@@ -286,7 +258,7 @@ __device__ __forceinline__ void g3_wave_main(
       const bool copy = ph + 1 < G3_NPH || has_next;
       const float *src = (ph + 1 < G3_NPH) ? xg + (size_t)(ph + 1) * G3_CP * row_stride : nxg;
       auto dma_piece = [&](int i) {
-        if (doff[i] >= 0) g3_dma16(src, doff[i], buf_nxt + (i * NW + wave) * 256);
+        if (doff[i] >= 0) tile_dma16(src, doff[i], buf_nxt + (i * NW + wave) * 256);
       };
 
       if constexpr (FORM == 0) {
@@ -313,7 +285,6 @@ __device__ __forceinline__ void g3_wave_main(
       const bool first = tile == (int)blockIdx.x;
       // two rows (q, q + 1) per instruction: the accumulator tile is four consecutive registers, so the differences,
       // sums and squares of a pair are one packed instruction each (VALU time is matrix-pipe time: half the count)
-      typedef float f32x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
       for (int m = 0; m < 4; ++m)
 #pragma unroll
@@ -498,12 +469,7 @@ __global__ __launch_bounds__(G3_NW * 64, 2) void gcn3_kernel(
   if (stats_partial) {
     __syncthreads();
     if constexpr (BWD) {          // [64][2] plain sums
-      if (tid < 128) {
-        float t = 0.f;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) t += rowstat[(w * 64 + (tid >> 1)) * G3_ST + (tid & 1)];
-        stats_partial[(size_t)blockIdx.x * 128 + tid] = t;
-      }
+      tile_write_sums<G3_ST>(rowstat, stats_partial, tid);
     } else if (tid < 64) {        // [64][3] = (count, mean, M2) of the workgroup's tiles: the eight waves' entries merged
       const int ntiles = (p.total_tiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
       const float per_joint = (float)(ntiles * G3_F);
@@ -534,14 +500,8 @@ int gcn3_launch(const G3Params &p, int ltot, int blocks, size_t lds, const float
                 const float *bias_cv, const float *addend, float *z, float *stats_partial, const float *bwd_u,
                 const unsigned char *bwd_mask, const float *bwd_fin, void *stream_h,
                 const unsigned char *addend_mask = nullptr) {
-  auto kern = gcn3_kernel<FORM, BWD, MADD>;
-  static unsigned char lds_ok[P2R_MAX_DEVICES];
-  hipError_t e = p2r_allow_big_lds(kern, lds_ok);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(G3_NW * 64), lds, p2r_stream(stream_h), p, ltot, x, Wp, coef, bias_cv, addend,
-                     z, stats_partial, bwd_u, bwd_mask, bwd_fin, addend_mask);
-  P2R_LAUNCH_CHECK();
-  return P2R_OK;
+  return p2r_launch_big_lds<gcn3_kernel<FORM, BWD, MADD>>(blocks, G3_NW * 64, lds, stream_h, p, ltot, x, Wp, coef, bias_cv,
+                                                          addend, z, stats_partial, bwd_u, bwd_mask, bwd_fin, addend_mask);
 }
 
 }  // namespace

@@ -19,23 +19,21 @@
 //     (64 rows) at once and two more do not fit the 160 KB, so the copy of the next tile starts when the last wave has
 //     finished the current one (the first generation staged through VGPRs in two dependent batches instead).
 //   * The bias-table gradient (sum of dZ over samples and frames per (channel, joint)) is taken from the resident tile.
-#include "p2r_common.h"
+#include "stgcn_tile.h"
 
 #include "gcn3_sched.inc"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
+// A tile of its own shape -- 4 frames x all 64 rows -- with the piece arithmetic of the shared tile (stgcn_tile.h)
 constexpr int W3_F = 4;                      // frames per tile = one MFMA k-step per joint
-constexpr int W3_V = G3_V;
-constexpr int W3_NW = 8;
+constexpr int W3_V = TILE_V;
+constexpr int W3_NW = TILE_NW;
 constexpr int W3_RL = W3_F * W3_V;           // 212 floats per row (848 bytes: 16-byte pieces)
 constexpr int W3_TILE = 64 * W3_RL;          // floats per tensor tile
 constexpr int W3_NV4 = W3_TILE / 4;          // 3392 float4 = 53 pieces of 64
-constexpr int W3_PIECES = (W3_NV4 + 63) / 64;
-constexpr int W3_PW = (W3_PIECES + W3_NW - 1) / W3_NW;      // 7 per wave and tensor
+constexpr int W3_PW = tile_pw(W3_NV4);       // 7 per wave and tensor
+static_assert(G3_V == TILE_V, "schedule generated for another skeleton");
 constexpr int W3_CS = (64 * W3_V + W3_NW * 64 - 1) / (W3_NW * 64);   // (channel, joint) sums owned per thread: 7
 
 struct W3Params {
@@ -46,16 +44,6 @@ struct W3Params {
 constexpr int w3_wave_set[W3_NW] = W3_WAVE_SET;
 constexpr int w3_wave_half[W3_NW] = W3_WAVE_HALF;
 constexpr int w3_set_planes[4][W3_MAXPL] = W3_SET_PLANES;
-
-__device__ __forceinline__ unsigned w3_lds_addr(const float *p) {
-  return (unsigned)(size_t)(const __attribute__((address_space(3))) float *)p;
-}
-__device__ __forceinline__ void w3_dma16(const float *base, unsigned voff, float *lds_dst) {
-  unsigned keep;
-  const unsigned dst = __builtin_amdgcn_readfirstlane(w3_lds_addr(lds_dst));
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(base), "s"(dst) : "memory");
-}
 
 // 8 MFMAs of one (plane, joint) unit: 4 m-tiles x 2 n-tiles, one k-step, accumulating in place (see stgcn_gcn3.hip)
 __device__ __forceinline__ void w3_mfma8(f32x4 (&acc)[2][4], const float (&a)[4], const f32x2 &b) {
@@ -143,7 +131,7 @@ __device__ __forceinline__ void w3_wave_main(const W3Params &p, float *lds, cons
   const char *xl = reinterpret_cast<const char *>(xs + r * RL + g * V);
   const char *dl = reinterpret_cast<const char *>(ds + (32 * HALF + r) * RL + g * V);
   unsigned cl_off = (unsigned)((coef_l - lds) * sizeof(float));
-  asm volatile("" : "+v"(cl_off));                    // opaque: see stgcn_gcn3.hip
+  asm volatile("" : "+v"(cl_off));                    // opaque: see stgcn_gcn3.hip (g3_wave_main)
   const char *cl = reinterpret_cast<const char *>(lds) + cl_off;
 
   // this wave's DMA pieces of a tile (same element offsets for both tensors)
@@ -152,7 +140,7 @@ __device__ __forceinline__ void w3_wave_main(const W3Params &p, float *lds, cons
   for (int i = 0; i < W3_PW; ++i) {
     const int pc = i * NW + wave, e = pc * 64 + lane;
     const int row = e / (RL / 4), c4 = e - row * (RL / 4);
-    doff[i] = (pc < W3_PIECES && e < W3_NV4) ? (unsigned)(((size_t)row * row_stride + 4 * c4) * sizeof(float)) : 0xffffffffu;
+    doff[i] = (pc < tile_pieces(W3_NV4) && e < W3_NV4) ? (unsigned)(((size_t)row * row_stride + 4 * c4) * sizeof(float)) : 0xffffffffu;
   }
   auto copy_tile = [&](int tile) {
     const int seq = tile / p.tiles_per_seq, t0 = (tile % p.tiles_per_seq) * W3_F;
@@ -161,8 +149,8 @@ __device__ __forceinline__ void w3_wave_main(const W3Params &p, float *lds, cons
 #pragma unroll
     for (int i = 0; i < W3_PW; ++i)
       if (doff[i] != 0xffffffffu) {
-        w3_dma16(xg, doff[i], xs + (i * NW + wave) * 256);
-        w3_dma16(dg, doff[i], ds + (i * NW + wave) * 256);
+        tile_dma16(xg, doff[i], xs + (i * NW + wave) * 256);
+        tile_dma16(dg, doff[i], ds + (i * NW + wave) * 256);
       }
   };
 
@@ -293,11 +281,5 @@ extern "C" int p2r_stgcn_gcn3_weight_grad(int N, int T, int V, int K, int ltot, 
   p.total_tiles = (int)tiles;
   const size_t lds = (size_t)2 * W3_TILE * sizeof(float) + (size_t)ltot * V * sizeof(float);
   if (lds > 160 * 1024) return P2R_EINVAL;
-  static unsigned char lds_ok[P2R_MAX_DEVICES];
-  hipError_t e = p2r_allow_big_lds(gcn3_dw_kernel, lds_ok);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(gcn3_dw_kernel, dim3(n_blocks), dim3(W3_NW * 64), lds, p2r_stream(stream), p, x, dz, coef,
-                     dw_partial, colsum_partial);
-  P2R_LAUNCH_CHECK();
-  return P2R_OK;
+  return p2r_launch_big_lds<gcn3_dw_kernel>(n_blocks, W3_NW * 64, lds, stream, p, x, dz, coef, dw_partial, colsum_partial);
 }

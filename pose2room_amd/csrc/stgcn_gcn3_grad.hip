@@ -18,7 +18,7 @@
 //     code generated at build time (tools/gen_gcn_sched.py, D3_BODY_<wave>), as in stgcn_gcn3.hip.
 //   * Each product is reduced over the wave with DPP row sums + two lane swaps; one lane accumulates it into the
 //     workgroup's LDS table [ltot][V] (owned entries: no contention), written out once per workgroup.
-#include "p2r_common.h"
+#include "stgcn_tile.h"
 
 #include "gcn3_sched.inc"
 
@@ -36,17 +36,10 @@ extern "C" int p2r_debug_d3_trace(unsigned long long *dst) {
 #endif
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int D3_F = 16;
-constexpr int D3_NW = 8;
-constexpr int D3_SLOTS = 7;
-constexpr int D3_V = G3_V;
-constexpr int D3_RS = D3_F * D3_V;          // 848
-constexpr int D3_BUF = 16 * D3_RS;          // floats per 16-row slice
-constexpr int D3_NV4 = D3_BUF / 4;
-constexpr int D3_PIECES = (D3_NV4 + 63) / 64;          // 53
-constexpr int D3_PW = (D3_PIECES + D3_NW - 1) / D3_NW; // 7
+// the shared tile (stgcn_tile.h); a slice here is 16 rows of dZ or X
+constexpr int D3_F = TILE_F, D3_NW = TILE_NW, D3_SLOTS = TILE_SLOTS, D3_V = TILE_V;
+constexpr int D3_RS = TILE_RS, D3_BUF = TILE_BUF, D3_NV4 = TILE_NV4, D3_PW = TILE_PW;
+static_assert(G3_V == TILE_V, "schedule generated for another skeleton");
 
 struct D3Params {
   int T, ltot;
@@ -55,16 +48,6 @@ struct D3Params {
 
 constexpr int d3_slot_joints[D3_NW][D3_SLOTS] = G3_SLOT_JOINTS_1;
 constexpr int d3_plane0[D3_NW] = G3_PLANE0_1;
-
-__device__ __forceinline__ unsigned d3_lds_addr(const float *p) {
-  return (unsigned)(size_t)(const __attribute__((address_space(3))) float *)p;
-}
-__device__ __forceinline__ void d3_dma16(const float *base, int voff, float *lds_dst) {
-  unsigned keep;
-  const unsigned dst = __builtin_amdgcn_readfirstlane(d3_lds_addr(lds_dst));
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(base), "s"(dst) : "memory");
-}
 
 // Y tile of one (plane, joint) unit: 16 k-steps (all 64 input channels) into ONE accumulator; the first MFMA starts
 // from the inline constant 0.  Two assembly blocks of 8 (operand-count limit of one asm statement).
@@ -109,8 +92,6 @@ __device__ __forceinline__ float d3_wave_sum(float v) {
   auto b = __builtin_amdgcn_permlane16_swap(__float_as_uint(s), __float_as_uint(s), false, false);
   return __uint_as_float(b[0]) + __uint_as_float(b[1]);
 }
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // Wave reduction of the step's per-lane products.  VALU work is matrix-pipe time on gfx950 (fp32 MFMAs issue through
 // the vector datapath), so the reduction is built to need as few vector instructions per entry as possible:
@@ -224,7 +205,7 @@ __device__ __forceinline__ void d3_wave_main(const D3Params &p, float *lds, cons
     const int e = pc * 64 + lane;
     const int lrow = e / (RS / 4), c4 = e - lrow * (RS / 4);
     const int row = 4 * (lrow & 3) + (lrow >> 2);
-    doff[i] = (pc < D3_PIECES && e < D3_NV4) ? (int)(((size_t)row * row_stride + 4 * c4) * sizeof(float)) : -1;
+    doff[i] = (pc < TILE_PIECES && e < D3_NV4) ? (int)(((size_t)row * row_stride + 4 * c4) * sizeof(float)) : -1;
   }
   float bz[SLOTS][16];                                // X[4 kk + g][frame r][joint of the slot]
   float aS[2][16];                                    // two A-operand sets: W_k[16 p + r][4 kk + g], kk = 0..15
@@ -244,7 +225,7 @@ __device__ __forceinline__ void d3_wave_main(const D3Params &p, float *lds, cons
     const float *dr = dz + (size_t)seq * 64 * row_stride + (size_t)t0 * V;
 #pragma unroll
     for (int i = 0; i < D3_PW; ++i)
-      if (doff[i] >= 0) d3_dma16(dr, doff[i], lds + (i * NW + wave) * 256);
+      if (doff[i] >= 0) tile_dma16(dr, doff[i], lds + (i * NW + wave) * 256);
   }
   load_a(aS[0], d3_plane0[WAVE], 0);
 
@@ -276,7 +257,7 @@ __device__ __forceinline__ void d3_wave_main(const D3Params &p, float *lds, cons
         __syncthreads();                                    // nobody reads buffer 1 any more
 #pragma unroll
         for (int i = 0; i < D3_PW; ++i)
-          if (doff[i] >= 0) d3_dma16(xs + (size_t)sl * 16 * row_stride, doff[i], xb + (i * NW + wave) * 256);
+          if (doff[i] >= 0) tile_dma16(xs + (size_t)sl * 16 * row_stride, doff[i], xb + (i * NW + wave) * 256);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
 #pragma unroll
@@ -302,7 +283,7 @@ __device__ __forceinline__ void d3_wave_main(const D3Params &p, float *lds, cons
       const bool copy = ph + 1 < 4 || has_next;
       const float *src = (ph + 1 < 4) ? dg + (size_t)(ph + 1) * 16 * row_stride : ndg;
       auto dma_piece = [&](int i) {
-        if (doff[i] >= 0) d3_dma16(src, doff[i], buf_nxt + (i * NW + wave) * 256);
+        if (doff[i] >= 0) tile_dma16(src, doff[i], buf_nxt + (i * NW + wave) * 256);
       };
       if constexpr (WAVE == 0) { D3_BODY_0 } else if constexpr (WAVE == 1) { D3_BODY_1 }
       else if constexpr (WAVE == 2) { D3_BODY_2 } else if constexpr (WAVE == 3) { D3_BODY_3 }
@@ -359,11 +340,5 @@ extern "C" int p2r_stgcn_gcn3_coef_grad(int N, int T, int V, int K, int ltot, co
   p.total_tiles = (int)tiles;
   const size_t lds = (size_t)2 * D3_BUF * sizeof(float) + (size_t)ltot * V * sizeof(float);
   if (lds > 160 * 1024) return P2R_EINVAL;
-  static unsigned char lds_ok[P2R_MAX_DEVICES];
-  hipError_t e = p2r_allow_big_lds(gcn3_dcoef_kernel, lds_ok);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(gcn3_dcoef_kernel, dim3(n_blocks), dim3(D3_NW * 64), lds, p2r_stream(stream), p, x, dz, Wp,
-                     dcoef_partial);
-  P2R_LAUNCH_CHECK();
-  return P2R_OK;
+  return p2r_launch_big_lds<gcn3_dcoef_kernel>(n_blocks, D3_NW * 64, lds, stream, p, x, dz, Wp, dcoef_partial);
 }

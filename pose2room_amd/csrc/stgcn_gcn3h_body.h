@@ -18,7 +18,7 @@
 //     16 of 32.
 // MFMAs through the compiler's builtin between scheduling fences and the split through plain conversions: every hazard
 // is the compiler's to track (the round-5 prototype used assembly blocks and found three ways to read stale registers).
-#include "p2r_common.h"
+#include "stgcn_tile.h"
 #include "split16.h"
 
 // H3_RES_SCALED (the data gradient: heavy-tailed operand, split16.h): the aggregate's residual part is kept scaled by
@@ -34,15 +34,11 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned h3_u4 __attribute__((ext_vector_type(4)));
 
-constexpr int H3_V = 53, H3_F = 16, H3_CP = 16, H3_NPH = 4, H3_NW = 8, H3_SLOTS = 7;
-constexpr int H3_RS = H3_F * H3_V;            // 848
-constexpr int H3_BUF = H3_CP * H3_RS;
-constexpr int H3_NV4 = H3_BUF / 4;
-constexpr int H3_PIECES = (H3_NV4 + 63) / 64;          // 53
-constexpr int H3_PW = (H3_PIECES + H3_NW - 1) / H3_NW; // 7
+// the shared tile (stgcn_tile.h) under the names the generated schedules and this file use
+constexpr int H3_V = TILE_V, H3_F = TILE_F, H3_CP = TILE_CP, H3_NPH = TILE_NPH, H3_NW = TILE_NW, H3_SLOTS = TILE_SLOTS;
+constexpr int H3_RS = TILE_RS, H3_BUF = TILE_BUF, H3_NV4 = TILE_NV4, H3_PW = TILE_PW;
 constexpr int H3_ST = 3;      // floats per (wave, row) statistics entry: (sum, sum of squares) about the pivot, pivot -- at the accumulators' scale
 constexpr int h3_slot_joints[H3_NW][H3_SLOTS] = H3_SLOT_JOINTS;
 constexpr int h3_plane0[H3_NW] = {H3_PLANE0_0, H3_PLANE0_1, H3_PLANE0_2, H3_PLANE0_3, H3_PLANE0_4, H3_PLANE0_5, H3_PLANE0_6, H3_PLANE0_7};
@@ -55,16 +51,6 @@ struct H3Params {
   const unsigned *x_amax;
   const float *winv;
 };
-
-__device__ __forceinline__ unsigned h3_lds_addr(const float *p) {
-  return (unsigned)(size_t)(const __attribute__((address_space(3))) float *)p;
-}
-__device__ __forceinline__ void h3_dma16(const float *base, int voff, float *lds_dst) {
-  unsigned keep;
-  const unsigned dst = __builtin_amdgcn_readfirstlane(h3_lds_addr(lds_dst));
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(base), "s"(dst) : "memory");
-}
 
 // the 12 MFMAs of a unit: a1 / a2 = the parts (w1, w2) of [W_a | W_b] rows 16 m + r, b1 / b2 = the parts of the aggregate
 // (H3_RES_SCALED: b2 = its residual scaled by 2^11, met by 2^-11 w1: split16.h)
@@ -151,7 +137,7 @@ __device__ __forceinline__ void h3_wave_main(const H3Params &p, float *lds, cons
                                              const p2r_h8 *__restrict__ Wp, float *__restrict__ z, float scale,
                                              float inv_scale) {
   constexpr int V = H3_V, F = H3_F, CP = H3_CP, NPH = H3_NPH, NW = H3_NW, SLOTS = H3_SLOTS, RS = H3_RS, BUF = H3_BUF;
-  constexpr int NV4 = H3_NV4, PIECES = H3_PIECES, PW = H3_PW, ST = H3_ST;
+  constexpr int NV4 = H3_NV4, PW = H3_PW, ST = H3_ST;
   constexpr int wave = WAVE;
   float *bias_l = lds + 2 * BUF;                       // [64][V]
   float *coef_l = bias_l + 64 * V;                     // [ltot + 1][V] (last row zeros)
@@ -162,7 +148,7 @@ __device__ __forceinline__ void h3_wave_main(const H3Params &p, float *lds, cons
   const size_t row_stride = (size_t)p.T * V;
   const char *xl0 = reinterpret_cast<const char *>(lds + g * RS + r * V);   // channels g + 4 i, frame r
   unsigned cl_off = (unsigned)((coef_l - lds) * sizeof(float));
-  asm volatile("" : "+v"(cl_off));                     // opaque base: see stgcn_gcn3.hip
+  asm volatile("" : "+v"(cl_off));                     // opaque base: see stgcn_gcn3.hip (g3_wave_main)
   const char *cl = reinterpret_cast<const char *>(lds) + cl_off;
 
   int doff[PW];
@@ -170,7 +156,7 @@ __device__ __forceinline__ void h3_wave_main(const H3Params &p, float *lds, cons
   for (int i = 0; i < PW; ++i) {
     const int pc = i * NW + wave, e = pc * 64 + lane;
     const int row = e / (RS / 4), c4 = e - row * (RS / 4);
-    doff[i] = (pc < PIECES && e < NV4) ? (int)(((size_t)row * row_stride + 4 * c4) * sizeof(float)) : -1;
+    doff[i] = (pc < TILE_PIECES && e < NV4) ? (int)(((size_t)row * row_stride + 4 * c4) * sizeof(float)) : -1;
   }
 
   f32x4 acc[SLOTS][4];
@@ -192,7 +178,7 @@ __device__ __forceinline__ void h3_wave_main(const H3Params &p, float *lds, cons
     const float *xr = x + (size_t)seq * 64 * row_stride + (size_t)t0 * V;
 #pragma unroll
     for (int i = 0; i < PW; ++i)
-      if (doff[i] >= 0) h3_dma16(xr, doff[i], lds + (i * NW + wave) * 256);
+      if (doff[i] >= 0) tile_dma16(xr, doff[i], lds + (i * NW + wave) * 256);
   }
   load_a(aS, h3_plane0[WAVE], 0);
 
@@ -224,7 +210,7 @@ __device__ __forceinline__ void h3_wave_main(const H3Params &p, float *lds, cons
       const bool copy = ph + 1 < NPH || has_next;
       const float *src = (ph + 1 < NPH) ? xg + (size_t)(ph + 1) * CP * row_stride : nxg;
       auto dma_piece = [&](int i) {
-        if (doff[i] >= 0) h3_dma16(src, doff[i], buf_nxt + (i * NW + wave) * 256);
+        if (doff[i] >= 0) tile_dma16(src, doff[i], buf_nxt + (i * NW + wave) * 256);
       };
       if constexpr (WAVE == 0) { H3_BODY_0 } else if constexpr (WAVE == 1) { H3_BODY_1 }
       else if constexpr (WAVE == 2) { H3_BODY_2 } else if constexpr (WAVE == 3) { H3_BODY_3 }
@@ -407,13 +393,8 @@ int h3_launch(int N, int T, const float *x, const void *Wp, const float *winv, c
   p.T = T; p.tiles_per_seq = T / H3_F; p.total_tiles = (int)tiles;
   p.stats = stats_partial; p.addend = addend; p.addend_mask = addend_mask; p.x_amax = x_amax; p.winv = winv;
   const size_t lds = ((size_t)2 * H3_BUF + 64 * H3_V + (size_t)(H3_LTOT + 1) * H3_V + H3_NW * 64 * H3_ST) * sizeof(float);
-  static unsigned char lds_ok[P2R_MAX_DEVICES];
-  hipError_t e = p2r_allow_big_lds(H3_KERNEL, lds_ok);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(H3_KERNEL, dim3(blocks), dim3(H3_NW * 64), lds, p2r_stream(stream), p, x,
-                     reinterpret_cast<const p2r_h8 *>(Wp), coef, bias_cv, z);
-  P2R_LAUNCH_CHECK();
-  return P2R_OK;
+  return p2r_launch_big_lds<H3_KERNEL>(blocks, H3_NW * 64, lds, stream, p, x, reinterpret_cast<const p2r_h8 *>(Wp), coef,
+                                       bias_cv, z);
 }
 
 }  // namespace

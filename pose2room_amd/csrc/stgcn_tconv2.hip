@@ -6,7 +6,7 @@
 // transform -- its data gradient):
 //     out[n,c,t,w] = bias[c] + sum_{p<3} sum_ci W[p][c][ci] * h[n,ci,t+p-1,w],   h = relu(x*scale+shift) or x, 0 outside [0,T)
 //
-// It runs on the skeleton of the second-generation graph convolution (stgcn_gcn2.hip), whose measurements it
+// It runs on the tile skeleton of the second-generation graph convolution (stgcn_tile.h), whose measurements it
 // inherits:
 //   * MFMA n-tile = 16 frames of ONE joint; the three taps are three "planes" whose B operand is the input shifted by
 //     one frame: lane (g = lane >> 4, r = lane & 15) reads channel 4s+g at frame r+p-1 of the joint -- no gather, no
@@ -21,39 +21,17 @@
 //     phases; the tile leaves through LDS as whole rows; the epilogue also emits per-channel (sum, sum of squares).
 // On gfx950 fp32 MFMAs and VALU work of the co-resident wave do not overlap, which is why the per-record work here is
 // four LDS reads at immediate offsets and nothing else.
-#include "p2r_common.h"
+#include "stgcn_tile.h"
 
 namespace {
 
-typedef float f32x4t __attribute__((ext_vector_type(4)));
-
-constexpr int T2_F = 16;            // frames per tile = columns of an MFMA n-tile
-constexpr int T2_CP = 16;           // channels per phase
-constexpr int T2_NPH = 4;
-constexpr int T2_NW = 8;            // waves per workgroup
-constexpr int T2_SLOTS = 7;         // joints per wave (consecutive)
+// the shared tile (stgcn_tile.h); the joints of a wave are consecutive here
+constexpr int T2_F = TILE_F, T2_CP = TILE_CP, T2_NPH = TILE_NPH, T2_NW = TILE_NW, T2_SLOTS = TILE_SLOTS;
 
 struct T2Params {
   int T, tiles_per_seq, total_tiles;
   int vec;                          // rows 16-byte aligned and T*V % 4 == 0: 16-byte DMA pieces for full tiles
 };
-
-__device__ __forceinline__ unsigned t2_lds_addr(const float *p) {
-  return (unsigned)(size_t)(const __attribute__((address_space(3))) float *)p;
-}
-// LDS-DMA as inline assembly (see stgcn_gcn2.hip: keeps hipcc from waiting for the copy in front of every LDS read)
-__device__ __forceinline__ void t2_dma16(const float *src, float *lds_dst) {
-  unsigned keep;
-  const unsigned dst = __builtin_amdgcn_readfirstlane(t2_lds_addr(lds_dst));
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
-}
-__device__ __forceinline__ void t2_dma4(const float *src, float *lds_dst) {
-  unsigned keep;
-  const unsigned dst = __builtin_amdgcn_readfirstlane(t2_lds_addr(lds_dst));
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
-}
 
 // BWD (data-gradient instance only): the statistics epilogue emits the two sums of the BatchNorm + ReLU backward
 // of the layer in front instead -- per channel sum g' and sum g' * zhat with g' = out where relu'(scale*z+shift),
@@ -114,8 +92,8 @@ __global__ __launch_bounds__(T2_NW * 64, 2) void tconv2_kernel(
 
   // ---- LDS-DMA of one phase slice ------------------------------------------------------------------------------
   constexpr int NV4 = MAIN / 4;
-  constexpr int PIECES16 = (NV4 + 63) / 64;           // 53
-  constexpr int PW16 = (PIECES16 + NW - 1) / NW;      // 7 per wave
+  constexpr int PIECES16 = tile_pieces(NV4);          // 53
+  constexpr int PW16 = tile_pw(NV4);                  // 7 per wave
   constexpr int PIECES4 = (MAIN + 63) / 64;           // 212
   constexpr int PW4 = (PIECES4 + NW - 1) / NW;        // 27 per wave
   constexpr int PIECESH = (HALO + 63) / 64;           // 27
@@ -129,7 +107,7 @@ __global__ __launch_bounds__(T2_NW * 64, 2) void tconv2_kernel(
       if (piece_i < PW16 && pc < PIECES16) {
         const int e = pc * 64 + lane;
         const int row = e / (RS / 4), c4 = e - row * (RS / 4);
-        if (e < NV4) t2_dma16(xrow0 + (size_t)row * row_stride + 4 * c4, buf + pc * 256);
+        if (e < NV4) tile_dma16(xrow0 + (size_t)row * row_stride + 4 * c4, buf + pc * 256);
       }
     } else {
       constexpr int PER = (PW4 + PW16 - 1) / PW16;
@@ -141,7 +119,7 @@ __global__ __launch_bounds__(T2_NW * 64, 2) void tconv2_kernel(
           const int e = pc * 64 + lane;
           const int row = e / RS, col = e - row * RS;
           if (e < MAIN) {
-            if (col < frames * V) t2_dma4(xrow0 + (size_t)row * row_stride + col, buf + pc * 64);
+            if (col < frames * V) tile_dma4(xrow0 + (size_t)row * row_stride + col, buf + pc * 64);
             else buf[e] = fillv;
           }
         }
@@ -156,22 +134,15 @@ __global__ __launch_bounds__(T2_NW * 64, 2) void tconv2_kernel(
       if (e < HALO) {
         const int row = e / HRS, q = e - row * HRS;
         const int h = q >= V ? 1 : 0, v = q - h * V;
-        if (h ? hi : lo) t2_dma4(xrow0 + (size_t)row * row_stride + (h ? RS : -V) + v, buf + MAIN + pc * 64);
+        if (h ? hi : lo) tile_dma4(xrow0 + (size_t)row * row_stride + (h ? RS : -V) + v, buf + MAIN + pc * 64);
         else buf[MAIN + e] = fillv;
       }
     }
   };
 
-  f32x4t acc[SLOTS][4];
+  f32x4 acc[SLOTS][4];
   float a_nxt[4][4];
-  auto load_a = [&](int tp, int ph) {
-    const float4 *wp = reinterpret_cast<const float4 *>(Wp) + ((size_t)(tp * T2_NPH + ph) * 4) * 64 + lane;
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      const float4 u = wp[m * 64];
-      a_nxt[m][0] = u.x; a_nxt[m][1] = u.y; a_nxt[m][2] = u.z; a_nxt[m][3] = u.w;
-    }
-  };
+  auto load_a = [&](int tp, int ph) { tile_load_a(a_nxt, Wp, tp, ph, lane); };      // a tap is a plane
 
   int tile = blockIdx.x;
   if (tile < p.total_tiles) {       // prologue: phase 0 of the first tile
@@ -418,12 +389,7 @@ __global__ __launch_bounds__(T2_NW * 64, 2) void tconv2_kernel(
 
   if (stats_partial) {
     __syncthreads();
-    if (tid < 128) {
-      float t = 0.f;
-#pragma unroll
-      for (int w = 0; w < NW; ++w) t += rowstat[w * 128 + tid];
-      stats_partial[(size_t)blockIdx.x * 128 + tid] = t;
-    }
+    tile_write_sums<2>(rowstat, stats_partial, tid);
   }
 }
 
@@ -438,14 +404,8 @@ template <bool XFORM, bool BWD, int TAPS>
 static int tconv2_launch(const T2Params &p, int blocks, size_t lds, const float *x, const float *scale,
                          const float *shift, const float *Wp, const float *bias, float *out, float *stats_partial,
                          const float *bwd_z, const float *bwd_fin, void *stream) {
-  auto kern = tconv2_kernel<53, XFORM, BWD, TAPS>;
-  static unsigned char lds_ok[P2R_MAX_DEVICES];
-  hipError_t e = p2r_allow_big_lds(kern, lds_ok);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(T2_NW * 64), lds, p2r_stream(stream), p, x, scale, shift, Wp, bias, out,
-                     stats_partial, bwd_z, bwd_fin);
-  P2R_LAUNCH_CHECK();
-  return P2R_OK;
+  return p2r_launch_big_lds<tconv2_kernel<53, XFORM, BWD, TAPS>>(blocks, T2_NW * 64, lds, stream, p, x, scale, shift, Wp, bias,
+                                                                 out, stats_partial, bwd_z, bwd_fin);
 }
 
 extern "C" int p2r_stgcn_tconv2_forward(int N, int T, int V, int taps, const float *x, const float *scale, const float *shift,

@@ -14,7 +14,7 @@
 // three tap visits of a 4.6 us phase, were still in flight at the phase's end.
 //
 // Full tiles of 16-byte aligned rows only (T % 16 == 0): anything else runs on stgcn_tconv2.hip.
-#include "p2r_common.h"
+#include "stgcn_tile.h"
 
 // Cycle trace (profiling hook, off in the product build): with -DP2R_CYCLE_TRACE the waves of workgroup 7 stamp
 // s_memtime at the section boundaries of their fourth tile; tools/dev_t3_trace.py reads the stamps back through
@@ -32,11 +32,10 @@ extern "C" int p2r_debug_t3_trace(unsigned long long *dst) {
 #endif
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int T3_F = 16, T3_CP = 16, T3_NPH = 4, T3_NW = 8, T3_SLOTS = 7, T3_V = 53;
+// the shared tile (stgcn_tile.h); the three-tap window below is this file's own
+constexpr int T3_F = TILE_F, T3_CP = TILE_CP, T3_NPH = TILE_NPH, T3_NW = TILE_NW, T3_SLOTS = TILE_SLOTS, T3_V = TILE_V;
 constexpr int T3_ST = 3;   // floats per (wave, row) statistics entry: (sum, sum of squares) about the pivot, pivot
-constexpr int T3_RS = T3_F * T3_V;                  // 848
+constexpr int T3_RS = TILE_RS;                      // 848
 // LDS image of a slice (round 5): 16 channel rows of T3_RSP floats; a row is a contiguous WINDOW of the tensor's channel
 // row -- [3 unused][frame t0-1][frames t0 .. t0+15][frame t0+16][19 unused] -- so the halo frames of the three-tap
 // instances arrive with the same 16-byte DMA stream as the slice itself (frame t0 sits 56 floats = 14 pieces into the
@@ -54,27 +53,12 @@ struct T3Params {
   int T, tiles_per_seq, total_tiles;
 };
 
-__device__ __forceinline__ unsigned t3_lds_addr(const float *p) {
-  return (unsigned)(size_t)(const __attribute__((address_space(3))) float *)p;
-}
-__device__ __forceinline__ void t3_dma16(const float *base, unsigned voff, float *lds_dst) {
-  unsigned keep;
-  const unsigned dst = __builtin_amdgcn_readfirstlane(t3_lds_addr(lds_dst));
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(base), "s"(dst) : "memory");
-}
-__device__ __forceinline__ void t3_dma4(const float *base, unsigned voff, float *lds_dst) {
-  unsigned keep;
-  const unsigned dst = __builtin_amdgcn_readfirstlane(t3_lds_addr(lds_dst));
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(base), "s"(dst) : "memory");
-}
 // A operands (the weights of one (tap, phase): 4 x 16 bytes per lane) live in registers the compiler does not
 // allocate -- the kernels are limited to v0..v223 (amdgpu_num_vgpr), set 0 = v[224:239], set 1 = v[240:255], named in
 // the assembly text -- and are waited for
 // explicitly.  Two reasons.  Left to the compiler, its s_waitcnt in front of their first use counts only the loads it
-// knows about -- vmcnt(0..4) -- while the hardware counter also holds the slice pieces issued after them by t3_dma16 /
-// t3_dma4; vector-memory operations retire in order, so every wave stood at the top of a visit until most of the NEXT
+// knows about -- vmcnt(0..4) -- while the hardware counter also holds the slice pieces issued after them by tile_dma16;
+// vector-memory operations retire in order, so every wave stood at the top of a visit until most of the NEXT
 // slice had arrived (all 256 workgroups at once: ~3 us of a 13 us phase).  With the count spelled out (the pieces
 // issued after the operands may stay in flight) the copy runs under the MFMAs.  And a load whose destination is a
 // compiler-visible register cannot be waited for by hand: the compiler considers the value present after the load
@@ -212,12 +196,12 @@ __device__ __forceinline__ void t3_wave_main(const T3Params &p, float *lds, cons
   auto copy_slice = [&](float *buf, const float *base, bool lo, bool hi) {
     if (TAPS == 1 || (lo && hi)) {
 #pragma unroll
-      for (int i = 0; i < N16; ++i) t3_dma16(base, moff[i], buf + (i * NW + wave) * 256);
+      for (int i = 0; i < N16; ++i) tile_dma16(base, moff[i], buf + (i * NW + wave) * 256);
     } else {
 #pragma unroll
       for (int i = 0; i < N16; ++i) {
         const bool outside = (((lmask >> i) & 1u) && !lo) || (((rmask >> i) & 1u) && !hi);
-        if (!outside) t3_dma16(base, moff[i], buf + (i * NW + wave) * 256);
+        if (!outside) tile_dma16(base, moff[i], buf + (i * NW + wave) * 256);
         else *reinterpret_cast<float4 *>(buf + (i * NW + wave) * 256 + lane * 4) = float4{fillv, fillv, fillv, fillv};
       }
     }
@@ -549,12 +533,7 @@ __global__ __launch_bounds__(T3_NW * 64, 2) __attribute__((amdgpu_num_vgpr(224))
   if (stats_partial) {
     __syncthreads();
     if constexpr (BWD) {          // [64][2] plain sums
-      if (tid < 128) {
-        float t = 0.f;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) t += rowstat[(w * 64 + (tid >> 1)) * T3_ST + (tid & 1)];
-        stats_partial[(size_t)blockIdx.x * 128 + tid] = t;
-      }
+      tile_write_sums<T3_ST>(rowstat, stats_partial, tid);
     } else if (tid < 64) {        // [64][3] = (count, mean, M2) of the workgroup's tiles: the eight waves' entries merged
       const int ntiles = (p.total_tiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
       const float per_joint = (float)(ntiles * T3_F);
@@ -585,14 +564,8 @@ template <bool XFORM, bool BWD, int TAPS, bool ADDCT = false>
 int tconv3_launch(const T3Params &p, int blocks, size_t lds, const float *x, const float *scale, const float *shift,
                   const float *Wp, const float *bias, float *out, float *stats_partial, const float *bwd_z,
                   const float *bwd_fin, void *stream, const float *add_ct = nullptr) {
-  auto kern = tconv3_kernel<XFORM, BWD, TAPS, ADDCT>;
-  static unsigned char lds_ok[P2R_MAX_DEVICES];
-  hipError_t e = p2r_allow_big_lds(kern, lds_ok);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(T3_NW * 64), lds, p2r_stream(stream), p, x, scale, shift, Wp, bias, out,
-                     stats_partial, bwd_z, bwd_fin, add_ct);
-  P2R_LAUNCH_CHECK();
-  return P2R_OK;
+  return p2r_launch_big_lds<tconv3_kernel<XFORM, BWD, TAPS, ADDCT>>(blocks, T3_NW * 64, lds, stream, p, x, scale, shift, Wp,
+                                                                    bias, out, stats_partial, bwd_z, bwd_fin, add_ct);
 }
 
 }  // namespace
