@@ -137,3 +137,155 @@ def seam_cotangents(B, seed=77):
     these through the reference's backbone, the GPU test through ours."""
     g = torch.Generator().manual_seed(seed)
     return torch.randn(B, 512, 3, generator=g), torch.randn(B, 512, 256, generator=g) * 0.1
+
+
+def graph_conv_reference(x, weight, bias, Aeff):
+    """the reference's ConvTemporalGraphical.forward in plain torch (conv1x1 + einsum), in the dtype of its arguments"""
+    K = Aeff.shape[0]
+    y = torch.nn.functional.conv2d(x, weight.view(K * 64, 64, 1, 1), bias)
+    n, kc, t, v = y.shape
+    return torch.einsum('nkctv,kvw->nctw', y.view(n, K, kc // K, t, v), Aeff)
+
+
+def ring_adjacency(K, V, seed):
+    """K planes over a V-joint ring skeleton: plane k links joints k hops apart (plus random extra links)."""
+    rng = np.random.RandomState(seed)
+    A = np.zeros((K, V, V), dtype=np.float32)
+    for k in range(K):
+        for v in range(V):
+            A[k, v, (v + k) % V] = rng.uniform(0.2, 1.0)
+            if rng.rand() < 0.3:
+                A[k, v, rng.randint(V)] = rng.uniform(0.2, 1.0)
+    return A
+
+
+def graph_conv_inputs(N, T, A, seed):
+    """(x, weight, bias, importance, cotangent) of one graph-conv call over the adjacency A (K, V, V), seeded on the CPU"""
+    K, V = A.shape[0], A.shape[1]
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(N, 64, T, V, generator=g)
+    w = torch.randn(K * 64, 64, generator=g) / 8
+    b = torch.randn(K * 64, generator=g) * 0.1
+    imp = 1 + 0.1 * torch.randn(K, V, V, generator=g)
+    go = torch.randn(N, 64, T, V, generator=g)
+    return x, w, b, imp, go
+
+
+def bn_conv_pair(taps, seed, dims=2):
+    """BatchNorm + 64 -> 64 convolution with `taps` temporal taps (dims=2: BatchNorm2d + Conv2d (taps,1); dims=1: BatchNorm1d
+    + Conv1d(1)), affine parameters and running statistics away from their defaults, seeded on the CPU"""
+    g = torch.Generator().manual_seed(seed)
+    if dims == 2:
+        bn, conv = torch.nn.BatchNorm2d(64), torch.nn.Conv2d(64, 64, (taps, 1), (1, 1), (taps // 2, 0))
+    else:
+        bn, conv = torch.nn.BatchNorm1d(64), torch.nn.Conv1d(64, 64, 1)
+    with torch.no_grad():
+        for t, lo, hi in ((bn.weight, 0.5, 1.5), (bn.bias, -0.5, 0.5), (bn.running_mean, -0.2, 0.2), (bn.running_var, 0.5, 2.0)):
+            t.copy_(torch.rand(t.shape, generator=g) * (hi - lo) + lo)
+        for t in (conv.weight, conv.bias):
+            t.copy_((torch.rand(t.shape, generator=g) * 2 - 1) / (64 * taps) ** 0.5)
+    return bn, conv
+
+
+def det_loss_scene(B, S, K, T, seed, case):
+    """(estimates, ground truth) of one detection-loss call; case: 'near' | 'random' | 'none' | 'ties' | 'single'"""
+    g = torch.Generator().manual_seed(seed)
+    J, G, NC = 53, 10, 22
+    r = lambda *s: torch.randn(*s, generator=g)
+    est = {
+        'seed_skeleton': r(B, S, J, 3) * 0.4 + torch.tensor([0.0, 0.9, 0.0]),
+        'vote_xyz': r(B, S, 3),
+        'seed_inds': torch.sort(torch.randint(0, T, (B, S), generator=g), 1)[0],
+        'aggregated_vote_xyz': r(B, K, 3),
+        'center': r(B, K, 3),
+        'size': r(B, K, 3) * 0.5,
+        'heading': r(B, K, 2).double(),
+        'objectness_scores': r(B, K, 2),
+        'sem_cls_scores': r(B, K, NC),
+    }
+    n_obj = torch.randint(1, G + 1, (B,), generator=g)
+    mask = (torch.arange(G)[None] < n_obj[:, None]).float()
+    centre = r(B, G, 3)
+    if case == 'near':          # GT centres next to aggregated votes: positives exist
+        for b in range(B):
+            for j in range(int(n_obj[b])):
+                centre[b, j] = est['aggregated_vote_xyz'][b, (7 * j + 1) % K] + 0.05
+    elif case == 'none':        # every proposal far from every GT box: no positive, n_pos = 1e-6
+        centre = centre + 50.0
+    elif case == 'ties':        # duplicated GT centres and proposals exactly on them: exact ties in every arg-min
+        centre[:, 1] = centre[:, 0]
+        est['aggregated_vote_xyz'][:, :4] = centre[:, :1]
+        est['center'][:, 5] = est['center'][:, 4]
+        n_obj = torch.clamp(n_obj, min=2)
+        mask = (torch.arange(G)[None] < n_obj[:, None]).float()
+    elif case == 'single':
+        mask = torch.zeros(B, G); mask[:, 0] = 1
+        centre[:, 0] = est['aggregated_vote_xyz'][:, 3]
+    m3 = mask[..., None]
+    gt = {
+        'center_label': centre * m3, 'box_label_mask': mask, 'size': r(B, G, 3) * 0.5 * m3,
+        'heading': r(B, G, 2) * m3, 'sem_cls_label': torch.randint(0, NC, (B, G), generator=g) * mask.long(),
+        'vote_label': r(B, T, J, 9) * 0.5, 'vote_label_mask': (torch.rand(B, T, J, generator=g) < 0.6).long(),
+    }
+    if case == 'ties':          # equal GT votes: the first of the three must win, like torch.min / argmin
+        gt['vote_label'][..., 3:6] = gt['vote_label'][..., 0:3]
+    return est, gt
+
+
+def seeded_randn(shape, seed, scale=1.0):
+    """standard normal values of one seed on the CPU, times `scale`"""
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(shape, generator=g) * scale
+
+
+def pw_gemm_case(B, L, K, R, x_nlc, bias):
+    """operands of one forward job of the point-wise GEMM: x (B,K,L) or (B,L,K), W (R,K), bias (R) or None, the input
+    transform fin [4,K] = (mean, invstd, scale, shift)"""
+    x = seeded_randn((B, L, K) if x_nlc else (B, K, L), 1)
+    W = seeded_randn((R, K), 2, 0.1)
+    bvec = seeded_randn((R,), 3) if bias else None
+    fin = torch.stack([seeded_randn((K,), 4), seeded_randn((K,), 5).abs() + 0.5, seeded_randn((K,), 6),
+                       seeded_randn((K,), 7)]).contiguous()
+    return x, W, bvec, fin
+
+
+def pw_data_gradient_case(B, L, K, R, x_nlc):
+    """operands of one data-gradient job: g, z (B,K,L) or (B,L,K), the layer's weight W [out = K][in = R], the lazy
+    BatchNorm-backward coefficients coef [3,K], the mask source mz (B,R,L) with its transform mfin [4,R]"""
+    g = seeded_randn((B, L, K) if x_nlc else (B, K, L), 1)
+    z = seeded_randn((B, L, K) if x_nlc else (B, K, L), 2)
+    W = seeded_randn((K, R), 3, 0.1)
+    coef = torch.stack([seeded_randn((K,), 4), seeded_randn((K,), 5), seeded_randn((K,), 6)]).contiguous()
+    mz = seeded_randn((B, R, L), 7)
+    mfin = torch.stack([seeded_randn((R,), 8), seeded_randn((R,), 9).abs() + 0.5, seeded_randn((R,), 10),
+                        seeded_randn((R,), 11)]).contiguous()
+    return g, z, W, coef, mz, mfin
+
+
+def pw_wgrad_case(B, L, R, K, x_nlc, y_nlc):
+    """operands of one weight-gradient job: g, z (B,R,L) or (B,L,R), y (B,K,L) or (B,L,K), coef [3,R], yfin [2,K]"""
+    g = seeded_randn((B, L, R) if x_nlc else (B, R, L), 1)
+    z = seeded_randn((B, L, R) if x_nlc else (B, R, L), 2)
+    y = seeded_randn((B, L, K) if y_nlc else (B, K, L), 3)
+    coef = torch.stack([seeded_randn((R,), 4), seeded_randn((R,), 5), seeded_randn((R,), 6)]).contiguous()
+    yfin = torch.stack([seeded_randn((K,), 7), seeded_randn((K,), 8)]).contiguous()
+    return g, z, y, coef, yfin
+
+
+def seed_indices(B, T, S, kind, seed=5):
+    """(B,S) int64 frame indices: 'sorted' distinct, 'dup' sorted with repeats, 'many' all within three frames, 'random'"""
+    g = torch.Generator().manual_seed(seed)
+    if kind == 'sorted':
+        return torch.sort(torch.stack([torch.randperm(T, generator=g)[:S] for _ in range(B)]), dim=1)[0]
+    if kind == 'many':        # far more seeds than frames: more hits per frame than the kernel's list holds
+        return torch.randint(0, 3, (B, S), generator=g)
+    inds = torch.randint(0, T, (B, S), generator=g)
+    return torch.sort(inds, dim=1)[0] if kind == 'dup' else inds
+
+
+def arc_length_case(B, T, S, g):
+    """cumulative arc lengths (B,T) with plateaus and exactly representable steps (exact ties), drawn from generator g"""
+    step = torch.rand(B, T - 1, generator=g)
+    step[torch.rand(B, T - 1, generator=g) < 0.3] = 0.0              # plateaus
+    step = (step * 8).round() / 8                                     # exactly representable: exact mid-point ties
+    return torch.cumsum(torch.cat([torch.zeros(B, 1), step], 1).double(), 1).float()

@@ -4,14 +4,9 @@ import numpy as np
 import pytest
 import torch
 
+from tests.cases import graph_conv_reference as _reference, ring_adjacency as _ring_adjacency
+
 pytestmark = pytest.mark.gpu
-
-
-def _reference(x, weight, bias, Aeff):
-    K = Aeff.shape[0]
-    y = torch.nn.functional.conv2d(x, weight.view(K * 64, 64, 1, 1), bias)
-    n, kc, t, v = y.shape
-    return torch.einsum('nkctv,kvw->nctw', y.view(n, K, kc // K, t, v), Aeff)
 
 
 # (5,1000): 315 tiles > 256 persistent workgroups, ragged last tile (second generation); T % 16 == 0: the statically
@@ -52,18 +47,6 @@ def test_graph_conv_forward_backward(dev, N, T):
     close(idv.grad, ir.grad, "d importance", 5e-5)
     # the gradient to zero-adjacency entries is exactly zero (support is preserved)
     assert (idv.grad.cpu()[At == 0] == 0).all()
-
-
-def _ring_adjacency(K, V, seed):
-    """K planes over a V-joint ring skeleton: plane k links joints k hops apart (plus random extra links)."""
-    rng = np.random.RandomState(seed)
-    A = np.zeros((K, V, V), dtype=np.float32)
-    for k in range(K):
-        for v in range(V):
-            A[k, v, (v + k) % V] = rng.uniform(0.2, 1.0)
-            if rng.rand() < 0.3:
-                A[k, v, rng.randint(V)] = rng.uniform(0.2, 1.0)
-    return A
 
 
 @pytest.mark.parametrize("V", [25, 17, 56])

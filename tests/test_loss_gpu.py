@@ -5,51 +5,9 @@ import numpy as np
 import pytest
 import torch
 
+from tests.cases import det_loss_scene as _scene
+
 pytestmark = pytest.mark.gpu
-
-
-def _scene(B, S, K, T, seed, case):
-    g = torch.Generator().manual_seed(seed)
-    J, G, NC = 53, 10, 22
-    r = lambda *s: torch.randn(*s, generator=g)
-    est = {
-        'seed_skeleton': r(B, S, J, 3) * 0.4 + torch.tensor([0.0, 0.9, 0.0]),
-        'vote_xyz': r(B, S, 3),
-        'seed_inds': torch.sort(torch.randint(0, T, (B, S), generator=g), 1)[0],
-        'aggregated_vote_xyz': r(B, K, 3),
-        'center': r(B, K, 3),
-        'size': r(B, K, 3) * 0.5,
-        'heading': r(B, K, 2).double(),
-        'objectness_scores': r(B, K, 2),
-        'sem_cls_scores': r(B, K, NC),
-    }
-    n_obj = torch.randint(1, G + 1, (B,), generator=g)
-    mask = (torch.arange(G)[None] < n_obj[:, None]).float()
-    centre = r(B, G, 3)
-    if case == 'near':          # GT centres next to aggregated votes: positives exist
-        for b in range(B):
-            for j in range(int(n_obj[b])):
-                centre[b, j] = est['aggregated_vote_xyz'][b, (7 * j + 1) % K] + 0.05
-    elif case == 'none':        # every proposal far from every GT box: no positive, n_pos = 1e-6
-        centre = centre + 50.0
-    elif case == 'ties':        # duplicated GT centres and proposals exactly on them: exact ties in every arg-min
-        centre[:, 1] = centre[:, 0]
-        est['aggregated_vote_xyz'][:, :4] = centre[:, :1]
-        est['center'][:, 5] = est['center'][:, 4]
-        n_obj = torch.clamp(n_obj, min=2)
-        mask = (torch.arange(G)[None] < n_obj[:, None]).float()
-    elif case == 'single':
-        mask = torch.zeros(B, G); mask[:, 0] = 1
-        centre[:, 0] = est['aggregated_vote_xyz'][:, 3]
-    m3 = mask[..., None]
-    gt = {
-        'center_label': centre * m3, 'box_label_mask': mask, 'size': r(B, G, 3) * 0.5 * m3,
-        'heading': r(B, G, 2) * m3, 'sem_cls_label': torch.randint(0, NC, (B, G), generator=g) * mask.long(),
-        'vote_label': r(B, T, J, 9) * 0.5, 'vote_label_mask': (torch.rand(B, T, J, generator=g) < 0.6).long(),
-    }
-    if case == 'ties':          # equal GT votes: the first of the three must win, like torch.min / argmin
-        gt['vote_label'][..., 3:6] = gt['vote_label'][..., 0:3]
-    return est, gt
 
 
 @pytest.mark.parametrize("B,S,K,T,case", [(2, 512, 128, 64, 'near'), (3, 100, 37, 16, 'random'), (2, 64, 128, 32, 'none'),

@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests import cases
+
 pytestmark = pytest.mark.gpu
 
 
@@ -15,8 +17,7 @@ def _rel(a, b):
 
 
 def _rand(shape, seed, dev, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return (torch.randn(shape, generator=g) * scale).to(dev)
+    return cases.seeded_randn(shape, seed, scale).to(dev)
 
 
 # ---- single kernels ---------------------------------------------------------------------------------------------------
@@ -27,11 +28,7 @@ def _rand(shape, seed, dev, scale=1.0):
 def test_pw_gemm_forward(dev, B, L, K, R, x_nlc, out_nlc, tr, bias):
     from pose2room_amd.p2rnet import pw_op
     from pose2room_amd import _lib
-    x = _rand((B, L, K) if x_nlc else (B, K, L), 1, dev)
-    W = _rand((R, K), 2, dev, 0.1)
-    bvec = _rand((R,), 3, dev) if bias else None
-    fin = torch.stack([_rand((K,), 4, dev), _rand((K,), 5, dev).abs() + 0.5, _rand((K,), 6, dev),
-                       _rand((K,), 7, dev)]).contiguous()
+    x, W, bvec, fin = (t.to(dev) if t is not None else None for t in cases.pw_gemm_case(B, L, K, R, x_nlc, bias))
     out = torch.empty((B, L, R) if out_nlc else (B, R, L), device=dev)
     stats = torch.empty((B * L // 64, R, 3), device=dev)
     job = dict(x=pw_op._at(x), w=pw_op._at(W), bias=pw_op._at(bvec), out=pw_op._at(out), stats=pw_op._at(stats), k=K, rows=R,
@@ -62,13 +59,7 @@ def test_pw_gemm_data_gradient(dev, B, L, K, R, x_nlc, lazy, out_nlc):
     """transposed weights, BatchNorm-backward input form, ReLU mask + BatchNorm-backward sums epilogue"""
     from pose2room_amd.p2rnet import pw_op
     from pose2room_amd import _lib
-    g = _rand((B, L, K) if x_nlc else (B, K, L), 1, dev)
-    z = _rand((B, L, K) if x_nlc else (B, K, L), 2, dev)
-    W = _rand((K, R), 3, dev, 0.1)             # the layer's weight [out = K][in = R]
-    coef = torch.stack([_rand((K,), 4, dev), _rand((K,), 5, dev), _rand((K,), 6, dev)]).contiguous()
-    mz = _rand((B, R, L), 7, dev)
-    mfin = torch.stack([_rand((R,), 8, dev), _rand((R,), 9, dev).abs() + 0.5, _rand((R,), 10, dev),
-                        _rand((R,), 11, dev)]).contiguous()
+    g, z, W, coef, mz, mfin = (t.to(dev) for t in cases.pw_data_gradient_case(B, L, K, R, x_nlc))
     out = torch.empty((B, L, R) if out_nlc else (B, R, L), device=dev)
     part = torch.empty((B * L // 64, R, 2), device=dev)
     job = dict(x=pw_op._at(g), x_nlc=x_nlc, x_ctot=K, w=pw_op._at(W), w_t=1, out=pw_op._at(out), out_ctot=R, out_nlc=out_nlc,
@@ -100,11 +91,7 @@ def test_pw_gemm_data_gradient(dev, B, L, K, R, x_nlc, lazy, out_nlc):
 def test_pw_wgrad(dev, B, L, R, K, x_nlc, y_nlc, lazy, ytr):
     from pose2room_amd.p2rnet import pw_op
     from pose2room_amd import _lib
-    g = _rand((B, L, R) if x_nlc else (B, R, L), 1, dev)
-    z = _rand((B, L, R) if x_nlc else (B, R, L), 2, dev)
-    y = _rand((B, L, K) if y_nlc else (B, K, L), 3, dev)
-    coef = torch.stack([_rand((R,), 4, dev), _rand((R,), 5, dev), _rand((R,), 6, dev)]).contiguous()
-    yfin = torch.stack([_rand((K,), 7, dev), _rand((K,), 8, dev)]).contiguous()
+    g, z, y, coef, yfin = (t.to(dev) for t in cases.pw_wgrad_case(B, L, R, K, x_nlc, y_nlc))
     chunks = B * L // 64
     for split in sorted({1, min(3, chunks), chunks}):
         pw = torch.full((split, R, K), float('nan'), device=dev)
@@ -299,16 +286,7 @@ def test_proposal_heads_generate_means_and_pi(dev):
                                             (1, 64, 256, 53, 512, 'random')])
 def test_seed_rows_match_advanced_indexing(dev, B, C, T, J, S, kind):
     from pose2room_amd.p2rnet import seed_op
-    g = torch.Generator().manual_seed(5)
-    if kind == 'sorted':
-        inds = torch.sort(torch.stack([torch.randperm(T, generator=g)[:S] for _ in range(B)]), dim=1)[0]
-    elif kind == 'many':        # far more seeds than frames: more hits per frame than the kernel's list holds
-        inds = torch.randint(0, 3, (B, S), generator=g)
-    else:
-        inds = torch.randint(0, T, (B, S), generator=g)
-        if kind == 'dup':
-            inds = torch.sort(inds, dim=1)[0]
-    inds = inds.to(dev)
+    inds = cases.seed_indices(B, T, S, kind).to(dev)
     x = _rand((B, C, T, J), 1, dev).requires_grad_(True)
     xr = x.detach().clone().requires_grad_(True)
     rows = seed_op.seed_rows(x, inds)
@@ -399,10 +377,7 @@ def test_nearest_prefix_equals_argmin_of_abs_difference(dev):
     from pose2room_amd.p2rnet import seed_op
     g = torch.Generator().manual_seed(9)
     for B, T, S in ((4, 256, 512), (3, 1024, 512), (2, 341, 100), (1, 2048, 512), (1, 20000, 64), (2, 40000, 16)):  # > 16384 frames: beyond the default 64 KB of LDS
-        step = torch.rand(B, T - 1, generator=g)
-        step[torch.rand(B, T - 1, generator=g) < 0.3] = 0.0              # plateaus
-        step = (step * 8).round() / 8                                     # exactly representable: exact mid-point ties
-        cum = torch.cumsum(torch.cat([torch.zeros(B, 1), step], 1).double(), 1).float().to(dev)
+        cum = cases.arc_length_case(B, T, S, g).to(dev)
         stride = cum[:, -1] / (S - 1)
         target = stride.unsqueeze(-1) * torch.arange(S, dtype=torch.float, device=dev)
         want = torch.argmin(torch.abs(cum.unsqueeze(-1) - target.unsqueeze(1)), dim=1)
