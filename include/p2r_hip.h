@@ -624,6 +624,27 @@ typedef struct p2r_mdn_sample_head {
 int p2r_mdn_sample(int nheads, const p2r_mdn_sample_head *heads, int B, int G, int L, int pi_ctot, int H,
                    const int *n_samples, unsigned long long seed, int h_offset, void *stream);
 
+/* The same sampler with a choice of read-out and the individual draws.  The value of draw s of hypothesis h is
+ *   v[h, b, l, s, d] = T(sum_g [u(h,b,l,g,s) < pi[b, g, l]] (mu[g, d] + sigma[g, d] eps(h,b,l,g,s,d)))
+ * -- components formed in the head's type T, added in double with g ascending, rounded once to T -- a function of
+ * (seed, head_id, hypothesis, row, s, d) alone.
+ *   readout 0 (mean)    out as p2r_mdn_sample writes it, bit for bit
+ *   readout 1 (median)  out[h, b, l, d] = the LOWER median of v[h, b, l, 0..n_h), the order statistic of rank
+ *                       (n_h - 1) / 2 (torch.median's choice): always one of the draws, never an average of two
+ *   draws (nullable, per head): (H, B, L, n_max, D) in T; v for s < n_h and 0 for n_h <= s < n_max, every element
+ *                       written.  n_max in 1..256 and >= every n_h when a head has a draws pointer; ignored otherwise.
+ * Everything else as p2r_mdn_sample. */
+typedef struct p2r_mdn_sample_head_ex {
+  const float *pi, *log_sigma;
+  const void *mu;
+  void *out, *draws;
+  int D, f64, head_id;
+} p2r_mdn_sample_head_ex;
+#define P2R_MDN_READOUT_MEAN 0
+#define P2R_MDN_READOUT_MEDIAN 1
+int p2r_mdn_sample_ex(int nheads, const p2r_mdn_sample_head_ex *heads, int B, int G, int L, int pi_ctot, int H,
+                      const int *n_samples, unsigned long long seed, int h_offset, int readout, int n_max, void *stream);
+
 /* Batch assembly from a device-resident sample store (csrc/batch_assemble.hip; the reference's dataloader.py:31-161,
  * `augment_data` + `__getitem__` + `collate_fn`, for one batch in one launch).  Store (all device memory, N samples,
  * F frames in all, J joints, K box slots):

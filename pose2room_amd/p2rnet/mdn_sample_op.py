@@ -1,13 +1,17 @@
-"""Bernoulli-gated mixture sampling for multi-hypothesis generation (csrc/mdn_sample.hip: p2r_mdn_sample).
+"""Bernoulli-gated mixture sampling for multi-hypothesis generation (csrc/mdn_sample.hip: p2r_mdn_sample,
+p2r_mdn_sample_ex).
 
 `sample(heads, pis, n_samples, seed, h_offset)` draws H hypotheses of up to three mixture heads in one launch:
 
     out[h, b, l, d] = (1 / n_h) sum_{s < n_h} sum_g [u(h,b,l,g,s) < pi[b,g,l]] (mu[g,d] + exp(log_sigma[g,d]) eps(h,b,l,g,s,d))
 
 -- `MixtureDensityHead.generate_point_predictions(pi, n_h, sample_pi=True)` (mdn.py:49-61, central tendency 'mean')
-with the draws taken from an in-kernel Philox4x32-10 stream instead of torch's generator.  `sample_reference` is the
-NumPy mirror of that stream (counter / key layout: the header comment of csrc/mdn_sample.hip); the kernel matches it to
-rounding, with identical gate decisions.
+with the draws taken from an in-kernel Philox4x32-10 stream instead of torch's generator.  `readout='median'` returns the
+lower median of the n_h draws instead (the order statistic of rank (n_h - 1) // 2, `torch.median`'s choice) and
+`return_draws=True` the draws themselves, `mdn.py`'s `generate_samples`: draw s of a hypothesis is the inner sum over g
+above, added in double with g ascending and rounded once to the head's type.  `sample_reference` is the NumPy mirror of
+that stream (counter / key layout: the header comment of csrc/mdn_sample.hip); the kernel matches it to rounding, with
+identical gate decisions.
 """
 import ctypes
 
@@ -24,8 +28,21 @@ PHILOX_W = (0x9E3779B9, 0xBB67AE85)
 MAX_HEADS, MAX_G, MAX_D, MAX_N = 3, 256, 4, 256
 
 
+READOUTS = {'mean': 0, 'median': 1}
+
+
 class _SampleHead(ctypes.Structure):
     _fields_ = [(n, _P) for n in ('pi', 'log_sigma', 'mu', 'out')] + [(n, _I) for n in ('D', 'f64', 'head_id')]
+
+
+class _SampleHeadEx(ctypes.Structure):
+    _fields_ = [(n, _P) for n in ('pi', 'log_sigma', 'mu', 'out', 'draws')] + [(n, _I) for n in ('D', 'f64', 'head_id')]
+
+
+def readout_code(readout):
+    if readout not in READOUTS:
+        raise ValueError(f"mdn_sample: readout must be 'mean' or 'median', got {readout!r}")
+    return READOUTS[readout]
 
 
 def _pi_layout(pis, G):
@@ -37,12 +54,15 @@ def _pi_layout(pis, G):
     return [p.contiguous() for p in pis], G
 
 
-def sample(heads, pis, n_samples, seed, h_offset=0, head_ids=None):
+def sample(heads, pis, n_samples, seed, h_offset=0, head_ids=None, readout='mean', return_draws=False):
     """heads: up to three MixtureDensityHead modules (their `mu`, `log_sigma`); pis: their (B, G, L) f32 mixture weights
     on one GPU (views into one tensor with a channel stride are passed as they are); n_samples: H counts in 1..256;
     seed: 64-bit int; h_offset: stream index of the first hypothesis; head_ids: stream index of each head (default
-    0, 1, 2 in order).  -> [out_i (H, B, L, D_i) in mu_i's dtype] -- per hypothesis the (B, K, D) memory order of
-    `pw_op.proposal_heads`' predictions."""
+    0, 1, 2 in order); readout: 'mean' or 'median' (the lower median of the n_h draws).
+    -> [out_i (H, B, L, D_i) in mu_i's dtype] -- per hypothesis the (B, K, D) memory order of `pw_op.proposal_heads`'
+    predictions; with return_draws ([out_i], [draws_i (H, B, L, Nmax, D_i)]), Nmax = max(n_samples), the slots
+    s >= n_h of hypothesis h zero."""
+    code = readout_code(readout)
     if not 1 <= len(heads) <= MAX_HEADS or len(pis) != len(heads):
         raise ValueError(f"mdn_sample: 1..{MAX_HEADS} heads with one pi each, got {len(heads)} / {len(pis)}")
     head_ids = list(range(len(heads))) if head_ids is None else list(head_ids)
@@ -58,7 +78,9 @@ def sample(heads, pis, n_samples, seed, h_offset=0, head_ids=None):
         raise RuntimeError("mdn_sample: at least one hypothesis")
     dev = pi0.device
     pis, ctot = _pi_layout(list(pis), G)
-    keep, outs, hs = [], [], []
+    ex = return_draws or code != 0          # the plain mean goes through the entry point it always had
+    n_max = max(ns) if return_draws else 0
+    keep, outs, hs, draws = [], [], [], []
     for i, (mdn, p) in enumerate(zip(heads, pis)):
         mu, ls = mdn.mu.detach(), mdn.log_sigma.detach()
         if mu.device != dev or ls.device != dev or mu.dtype not in (torch.float32, torch.float64) or \
@@ -69,15 +91,23 @@ def sample(heads, pis, n_samples, seed, h_offset=0, head_ids=None):
         out = torch.empty((H, B, L, D), dtype=mu.dtype, device=dev)
         keep += [mu, ls]
         outs.append(out)
-        hs.append(_SampleHead(pi=_lib.ptr(p), log_sigma=_lib.ptr(ls), mu=_lib.ptr(mu), out=_lib.ptr(out), D=D,
-                              f64=int(mu.dtype == torch.float64), head_id=head_ids[i]))
-    arr = (_SampleHead * len(hs))(*hs)
+        fields = dict(pi=_lib.ptr(p), log_sigma=_lib.ptr(ls), mu=_lib.ptr(mu), out=_lib.ptr(out), D=D,
+                      f64=int(mu.dtype == torch.float64), head_id=head_ids[i])
+        if return_draws:
+            draws.append(torch.empty((H, B, L, n_max, D), dtype=mu.dtype, device=dev))
+            fields['draws'] = _lib.ptr(draws[-1])
+        hs.append(_SampleHeadEx(**fields) if ex else _SampleHead(**fields))
+    arr = (type(hs[0]) * len(hs))(*hs)
     narr = (ctypes.c_int * H)(*ns)
+    key = ctypes.c_ulonglong(int(seed) & 0xffffffffffffffff)
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().p2r_mdn_sample(len(hs), arr, B, G, L, ctot, H, narr,
-                                             ctypes.c_ulonglong(int(seed) & 0xffffffffffffffff), int(h_offset),
-                                             _lib.current_stream(dev)), "mdn_sample")
-    return outs
+        if ex:
+            _lib.check(_lib.lib().p2r_mdn_sample_ex(len(hs), arr, B, G, L, ctot, H, narr, key, int(h_offset), code, n_max,
+                                                    _lib.current_stream(dev)), "mdn_sample_ex")
+        else:
+            _lib.check(_lib.lib().p2r_mdn_sample(len(hs), arr, B, G, L, ctot, H, narr, key, int(h_offset),
+                                                 _lib.current_stream(dev)), "mdn_sample")
+    return (outs, draws) if return_draws else outs
 
 
 def resolve_draws(num_hypotheses, n_samples=None, seed=None):
@@ -140,9 +170,12 @@ def _box_muller_f64(u1, u2):
     return r * np.cos(ang), r * np.sin(ang)
 
 
-def sample_reference(pi, mu, log_sigma, n_samples, seed, h_offset=0, head_id=0):
+def sample_reference(pi, mu, log_sigma, n_samples, seed, h_offset=0, head_id=0, readout='mean', return_draws=False):
     """Host mirror of one head of `sample`: pi (B, G, L) f32, mu [G][D] f32 or f64, log_sigma [G][D] f32 (NumPy arrays)
-    -> (H, B, L, D) in mu's dtype.  Same counters, same gate decisions; sums in double in another order."""
+    -> (H, B, L, D) in mu's dtype, with return_draws (that, draws (H, B, L, max(n_samples), D)).  Same counters, same
+    gate decisions; the mean's sums in double in another order; a draw is the sum over g in double, g ascending,
+    rounded to mu's dtype, and the median `np.sort` of the draws at (n - 1) // 2."""
+    code = readout_code(readout)
     pi = np.asarray(pi, dtype=np.float32)
     mu = np.asarray(mu)
     ls = np.asarray(log_sigma, dtype=np.float32)
@@ -155,6 +188,7 @@ def sample_reference(pi, mu, log_sigma, n_samples, seed, h_offset=0, head_id=0):
     k0, k1 = np.uint32(seed & 0xffffffff), np.uint32((seed >> 32) & 0xffffffff)
     ns = [int(n) for n in np.atleast_1d(np.asarray(n_samples))]
     out = np.empty((len(ns), B, L, D), dtype=mu.dtype)
+    draws = np.zeros((len(ns), B, L, max(ns), D), dtype=mu.dtype) if return_draws else None
     row = np.arange(rows, dtype=np.uint32)[:, None, None]
     g = np.arange(G, dtype=np.uint32)[None, :, None]
     for i, n in enumerate(ns):
@@ -176,6 +210,17 @@ def sample_reference(pi, mu, log_sigma, n_samples, seed, h_offset=0, head_id=0):
                 eps += list(_box_muller_f32(_u24(y[0]), _u24(y[1])))
         for d in range(D):
             comp = mu[:, d].astype(mu.dtype)[None, :, None] + sigma[:, d].astype(mu.dtype)[None, :, None] * eps[d]
-            tot = np.where(gate, comp.astype(np.float64), 0.0).sum(axis=(1, 2))
-            out[i, :, :, d] = (tot / n).astype(mu.dtype).reshape(B, L)
-    return out
+            gated = np.where(gate, comp.astype(np.float64), 0.0)
+            if code == 0:
+                tot = gated.sum(axis=(1, 2))
+                out[i, :, :, d] = (tot / n).astype(mu.dtype).reshape(B, L)
+            if code != 0 or return_draws:
+                v = np.zeros((rows, n), dtype=np.float64)
+                for gi in range(G):                                        # g ascending, one addition each
+                    v = v + gated[:, gi, :]
+                v = v.astype(mu.dtype)
+                if code != 0:
+                    out[i, :, :, d] = np.sort(v, axis=1)[:, (n - 1) // 2].reshape(B, L)
+                if return_draws:
+                    draws[i, :, :, :n, d] = v.reshape(B, L, n)
+    return (out, draws) if return_draws else out

@@ -120,13 +120,18 @@ class P2RNet(BaseNetwork):
             eval_dict['batch_gt_map_cls'] = assembly_gt_map_cls(parsed_gts)
         return end_points, eval_dict, parsed_predictions
 
-    def generate_hypotheses(self, data, num_hypotheses, n_samples=None, seed=None, eval=True):
+    def generate_hypotheses(self, data, num_hypotheses, n_samples=None, seed=None, eval=True, central_tendency=None,
+                            return_draws=False):
         """Multi-modal generation (the reference's `multi_mode`, proposal_net.py:56-59 / mdn.py:116-125): H hypotheses
-        of the detection for one batch, each one `generate` whose mixture heads return the mean of n_h Bernoulli-gated
-        draws.  The trunk runs once; the draws of all heads and hypotheses are one kernel launch (mdn_sample_op) and the
-        predictions of all hypotheses are parsed / NMS-ed as one H * B batch.
+        of the detection for one batch, each one `generate` whose mixture heads return the mean (or the median) of n_h
+        Bernoulli-gated draws.  The trunk runs once; the draws of all heads and hypotheses are one kernel launch
+        (mdn_sample_op) and the predictions of all hypotheses are parsed / NMS-ed as one H * B batch.
           n_samples: None -> each n_h uniform in 1..99 drawn from `seed`; an int or a length-H sequence fixes them.
           seed: None -> a 64-bit seed drawn from torch's default CPU generator (`torch.manual_seed` reproduces a call).
+          central_tendency: None -> each head's own `hparams.central_tendency`; 'mean' or 'median' (the lower median,
+          `torch.median`'s) overrides it for this call, the modules stay as they are.
+          return_draws: each hypothesis' end_points gain 'draws' = {'center', 'size', 'heading'}, the heads' individual
+          draws (B, K, n_h, D) (the centre's before the vote position is added).
         -> list of H (end_points, eval_dict, parsed_predictions) triples shaped like `generate`'s result; the
         deterministic end points (votes, aggregation, 'pi', objectness, class scores) are shared by all of them."""
         from ...net_utils.ap_helper import (parse_predictions, parse_groundtruths,
@@ -135,7 +140,8 @@ class P2RNet(BaseNetwork):
         seed, ns = mdn_sample_op.resolve_draws(num_hypotheses, n_samples, seed)
         H = len(ns)
         xyz, features, end_points = self._votes(data)
-        end_points, stacked, _ = self.detection.generate_hypotheses(xyz, features, end_points, H, ns, seed)
+        end_points, stacked, _, *draws = self.detection.generate_hypotheses(
+            xyz, features, end_points, H, ns, seed, central_tendency=central_tendency, return_draws=return_draws)
         B = end_points['aggregated_vote_xyz'].shape[0]
         joints = data['input_joints']
         gt_stacked = {'input_joints': joints.unsqueeze(0).expand(H, *joints.shape).reshape(H * B, *joints.shape[1:])}
@@ -147,6 +153,8 @@ class P2RNet(BaseNetwork):
             ep = dict(end_points)
             for k in ('center', 'size', 'heading'):
                 ep[k] = stacked[k][sl]
+            if return_draws:
+                ep['draws'] = {k: d[h, :, :, :ns[h]] for k, d in zip(('center', 'size', 'heading'), draws[0])}
             eval_dict = assembly_pred_map_cls({'pred_mask': eval_all['pred_mask'][sl]},
                                               {k: v[sl] for k, v in parsed_all.items()}, self.cfg.eval_config)
             if eval:

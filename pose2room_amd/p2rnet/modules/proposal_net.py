@@ -80,6 +80,8 @@ class ProposalNet(nn.Module):
             SingleConv(128, sem_obj_dim, kernel_size=1, order='c', num_groups=8, padding=0, ndim=1))
 
         G = cfg.config['data']['num_gaussian']
+        # read-out of the mixture heads' sampled predictions: 'mean' (the reference's only setting) or 'median'
+        self.central_tendency = (cfg.config.get('generation') or {}).get('central_tendency', 'mean')
         self.gmm_center = self.load_gmm(G, gmm_dim, 3, 'center')
         self.gmm_size = self.load_gmm(G, gmm_dim, 3, 'size')
         self.gmm_heading = self.load_gmm(G, gmm_dim, 2, 'heading')
@@ -122,7 +124,7 @@ class ProposalNet(nn.Module):
     def load_gmm(self, num_gaussian, in_dim, out_dim, type):
         mdn_config = Struct(num_gaussian=num_gaussian, out_dim=out_dim,
                             mu_bias_init=self.init_mu(num_gaussian, type), n_samples=1,
-                            central_tendency='mean')
+                            central_tendency=self.central_tendency)
         config = Struct(embedding_dims=[], out_dim=3, continuous_dim=in_dim,
                         batch_norm_continuous_input=False, hidden_dim=128, mdn_config=mdn_config)
         return CategoryEmbeddingMDN(config)
@@ -184,15 +186,22 @@ class ProposalNet(nn.Module):
         end_points['pi'] = {'center': pi_center, 'size': pi_size, 'heading': pi_heading}
         return end_points, (features.transpose(1, 2).contiguous() if export_proposal_feature else None)
 
-    def generate_hypotheses(self, xyz, features, end_points, num_hypotheses, n_samples, seed):
+    def generate_hypotheses(self, xyz, features, end_points, num_hypotheses, n_samples, seed, central_tendency=None,
+                            return_draws=False):
         """Multi-mode generation without re-running the trunk: the deterministic part (vote aggregation, stems,
         mixture weights pi, objectness and class scores) once, then every head's Bernoulli-gated mixture draws for
         all H hypotheses in one launch (csrc/mdn_sample.hip).  n_samples: H counts, seed: 64-bit stream key.
+        Each head is read out with its own `hparams.central_tendency` ('mean' or 'median', the lower median of its
+        draws; heads that disagree take one launch per read-out, which does not change a draw); central_tendency
+        overrides it for this call.
         -> (end_points shared by every hypothesis, with 'pi'; stacked end points of the H * B batch for
-        `parse_predictions`, hypothesis-major; the predictions (H, B, K, D) of the centre, size and heading heads)."""
-        for gm in (self.gmm_center, self.gmm_size, self.gmm_heading):
-            if gm.mdn.hparams.central_tendency != 'mean':
-                raise NotImplementedError("generate_hypotheses samples the 'mean' central tendency only")
+        `parse_predictions`, hypothesis-major; the predictions (H, B, K, D) of the centre, size and heading heads);
+        with return_draws also the heads' draws (H, B, K, max(n_samples), D), zero beyond each hypothesis' n_h."""
+        gmms = (self.gmm_center, self.gmm_size, self.gmm_heading)
+        readouts = [gm.mdn.hparams.central_tendency if central_tendency is None else central_tendency for gm in gmms]
+        for ro in readouts:
+            if ro not in ('mean', 'median'):
+                raise ValueError(f"generate_hypotheses: central_tendency must be 'mean' or 'median', got {ro!r}")
         features = self._aggregate(xyz, features, end_points)
         from .. import pw_op, mdn_sample_op
         if USE_FUSED_HEADS and pw_op.proposal_heads_supported(self, features):
@@ -205,10 +214,16 @@ class ProposalNet(nn.Module):
         sem_obj = sem_obj_feature.transpose(2, 1)
         end_points['objectness_scores'] = sem_obj[..., 0:2]
         end_points['sem_cls_scores'] = sem_obj[..., 2:]
-        preds = mdn_sample_op.sample([self.gmm_center.mdn, self.gmm_size.mdn, self.gmm_heading.mdn], list(pis),
-                                     n_samples, seed)
+        preds, draws = [None] * 3, [None] * 3
+        for ro in sorted(set(readouts)):
+            ids = [j for j in range(3) if readouts[j] == ro]
+            res = mdn_sample_op.sample([gmms[j].mdn for j in ids], [pis[j] for j in ids], n_samples, seed, head_ids=ids,
+                                       readout=ro, return_draws=return_draws)
+            for k, j in enumerate(ids):
+                preds[j] = res[0][k] if return_draws else res[k]
+                draws[j] = res[1][k] if return_draws else None
         H, (B, _, K) = len(n_samples), sem_obj_feature.shape
         stack = lambda t: t.unsqueeze(0).expand(H, *t.shape).reshape(H * B, *t.shape[1:])    # noqa: E731
         stacked = decode_scores(*[p.reshape(H * B, K, -1).transpose(1, 2) for p in preds], stack(sem_obj_feature),
                                 {'aggregated_vote_xyz': stack(end_points['aggregated_vote_xyz'])})
-        return end_points, stacked, preds
+        return (end_points, stacked, preds, draws) if return_draws else (end_points, stacked, preds)

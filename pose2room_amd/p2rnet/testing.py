@@ -115,15 +115,16 @@ def test(cfg, tester, batches, ap_device='cpu'):
 
 
 def test_multi_modal(cfg, net, batches, num_hypotheses, n_samples=None, seed=None, ap_device='cpu',
-                     dump_threshold=0.5):
+                     dump_threshold=0.5, central_tendency=None):
     """Multi-modal evaluation: what `num_hypotheses` reference test runs in multi mode plus
     utils/eval/multi_modal_eval.py produce, from one trunk pass per batch (`P2RNet.generate_hypotheses`).
     Hypothesis h plays run h: its sample counts n_h are fixed for all batches (drawn once from `seed` when None, as
     the reference draws one count per run), one `APCalculator` per IoU threshold collects its detections, and its
     confident boxes (dump_threshold: the reference's generation.dump_threshold) are its dump records.
-    net: P2RNet (or a wrapper exposing it as `.module`).
+    net: P2RNet (or a wrapper exposing it as `.module`).  central_tendency: None (the heads' own), 'mean' or 'median'.
     -> {'best_map': (T,) max over hypotheses of each threshold's mAP, 'tmd': mean TMD over every (sample, proposal),
-        'metrics': [h][t] metric dicts, 'n_samples': [n_h], 'seed': the 64-bit seed}."""
+        'metrics': [h][t] metric dicts, 'n_samples': [n_h], 'seed': the 64-bit seed,
+        'central_tendency': as passed}."""
     from ..net_utils import multi_modal_eval as mm
     from .mdn_sample_op import resolve_draws
     model = getattr(net, 'module', net)
@@ -137,7 +138,8 @@ def test_multi_modal(cfg, net, batches, num_hypotheses, n_samples=None, seed=Non
     with torch.no_grad():
         for i, data in enumerate(batches):
             batch_seed = (seed + i * 0x9E3779B97F4A7C15) & 0xffffffffffffffff     # one stream key per batch
-            for h, (ep, eval_dict, parsed) in enumerate(model.generate_hypotheses(data, H, ns, batch_seed, eval=True)):
+            for h, (ep, eval_dict, parsed) in enumerate(model.generate_hypotheses(
+                    data, H, ns, batch_seed, eval=True, central_tendency=central_tendency)):
                 for calc in calcs[h]:
                     calc.step(eval_dict['batch_pred_map_cls'], eval_dict['batch_gt_map_cls'])
                 records[h] += mm.confident_boxes(ep, eval_dict, parsed, dump_threshold)
@@ -147,4 +149,5 @@ def test_multi_modal(cfg, net, batches, num_hypotheses, n_samples=None, seed=Non
         cfg.log_string('multi-modal (%d hypotheses) iou_thresh %f: best mAP %f' % (H, thr, v))
     t = mm.tmd(records)
     cfg.log_string('multi-modal TMD: %f' % t)
-    return {'best_map': best, 'tmd': t, 'metrics': metrics, 'n_samples': ns, 'seed': seed}
+    return {'best_map': best, 'tmd': t, 'metrics': metrics, 'n_samples': ns, 'seed': seed,
+            'central_tendency': central_tendency}
