@@ -3,8 +3,18 @@
 The library is built in-tree by `pose2room_amd/csrc/Makefile`
 (`__graft_entry__.build()`).  Loading fails loudly: there is no Python or CPU
 fallback for any entry point.
+
+The header is the one declaration of the ABI: `prototypes()` parses it into the `argtypes` / `restype` of every entry
+point, `struct()` into the `ctypes.Structure` of every `typedef struct`, and `launch` / `launch_on` check a call
+against its prototype before anything is enqueued.  The parser is no C parser.  It reads the subset the header uses
+-- `/* */` comments, preprocessor lines, `typedef struct { ... } name;` blocks of pointer / int / long long / double
+fields, and prototypes `type p2r_name(type name, ...);` over int, float, double, long long, unsigned long long and
+pointers -- and raises P2RLibraryError, naming the declaration, on anything else.
 """
+import collections
 import ctypes
+import keyword
+import numbers
 import os
 import re
 
@@ -23,12 +33,115 @@ class P2RLibraryError(RuntimeError):
     pass
 
 
+# ---- the header ---------------------------------------------------------------------------------------------------------
+_SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double,
+            "long long": ctypes.c_longlong, "unsigned long long": ctypes.c_ulonglong}
+_KINDS = {ctypes.c_int: "i", ctypes.c_longlong: "i", ctypes.c_ulonglong: "i", ctypes.c_float: "f",
+          ctypes.c_double: "f", ctypes.c_void_p: "p"}
+_STRUCT_RE = re.compile(r"typedef\s+struct\s*\w*\s*\{([^{}]*)\}\s*(\w+)\s*;")
+_PROTO_RE = re.compile(r"([A-Za-z_][\w\s]*?[\s\*]+)(p2r_[a-z0-9_]+)\s*\(([^()]*)\)\s*;")
+
+# one entry point: kinds = 'i' (integer) / 'f' (floating) / 'p' (pointer) per parameter in front of the stream; pointer =
+# the same as one flag per parameter, scalars = the positions of the others (what `marshal` walks)
+Prototype = collections.namedtuple("Prototype", "name text restype argtypes kinds has_stream pointer scalars")
+
+
+def _code(header_path):
+    """the header without comments and preprocessor lines"""
+    with open(header_path) as f:
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    return re.sub(r"^\s*#.*$", "", text, flags=re.M)
+
+
 def declared_symbols(header_path=HEADER_PATH):
     """Names of every function the C header declares (used by the export test)."""
-    with open(header_path) as f:
-        text = f.read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(p2r_[a-z0-9_]+)\s*\(", text)))
+    return sorted(set(re.findall(r"\b(p2r_[a-z0-9_]+)\s*\(", _code(header_path))))
+
+
+def _ctype(decl, what):
+    """`decl` = a parameter or field declaration without its name: anything with a `*` is a pointer"""
+    if "*" in decl:
+        return ctypes.c_void_p
+    base = " ".join(t for t in decl.split() if t != "const")
+    if base not in _SCALARS:
+        raise P2RLibraryError(f"include/p2r_hip.h: type '{base}' in `{what}` is outside the subset the binding maps "
+                              f"({', '.join(_SCALARS)}, pointers)")
+    return _SCALARS[base]
+
+
+def _parse_prototype(ret, name, params):
+    text = " ".join(f"{ret.strip()} {name}({params});".split())
+    ret = " ".join(ret.split())
+    if ret == "const char *":
+        restype = ctypes.c_char_p
+    elif "*" in ret:
+        raise P2RLibraryError(f"include/p2r_hip.h: return type '{ret}' of `{text}` is outside the subset the binding maps")
+    else:
+        restype = _ctype(ret, text)
+    argtypes, names = [], []
+    if params.strip() != "void":
+        for p in params.split(","):
+            m = re.fullmatch(r"\s*(.*?[\s\*])(\w+)\s*", p, flags=re.S)
+            if m is None:
+                raise P2RLibraryError(f"include/p2r_hip.h: cannot read parameter '{p.strip()}' of `{text}`")
+            argtypes.append(_ctype(m.group(1), text))
+            names.append(m.group(2))
+    has_stream = bool(names) and names[-1] in ("stream", "stream_h") and argtypes[-1] is ctypes.c_void_p
+    kinds = "".join(_KINDS[t] for t in (argtypes[:-1] if has_stream else argtypes))
+    return Prototype(name, text, restype, tuple(argtypes), kinds, has_stream, tuple(k == "p" for k in kinds),
+                     tuple(i for i, k in enumerate(kinds) if k != "p"))
+
+
+def _parse_struct(body, name):
+    fields = []
+    for decl in body.split(";"):
+        if not decl.strip():
+            continue
+        first, *more = decl.split(",")
+        m = re.fullmatch(r"\s*(.*?[\s\*])(\w+)\s*", first, flags=re.S)
+        if m is None:
+            raise P2RLibraryError(f"include/p2r_hip.h: cannot read field '{decl.strip()}' of struct {name}")
+        base = m.group(1).replace("*", " ")
+        pieces = [(m.group(1), m.group(2))]
+        for d in more:       # further declarators of the line share the base type: `const float *x, *x2;`
+            m = re.fullmatch(r"\s*(\**)\s*(\w+)\s*", d)
+            if m is None:
+                raise P2RLibraryError(f"include/p2r_hip.h: cannot read field '{decl.strip()}' of struct {name}")
+            pieces.append((base + m.group(1), m.group(2)))
+        for typ, field in pieces:
+            fields.append((field + "_" if keyword.iskeyword(field) else field, _ctype(typ, f"struct {name}: {decl.strip()}")))
+    return type(name, (ctypes.Structure,), {"_fields_": fields})
+
+
+def _parse(header_path):
+    code = _code(header_path)
+    structs = {m.group(2): _parse_struct(m.group(1), m.group(2)) for m in _STRUCT_RE.finditer(code)}
+    protos = {m.group(2): _parse_prototype(*m.groups()) for m in _PROTO_RE.finditer(_STRUCT_RE.sub("", code))}
+    unread = sorted(set(declared_symbols(header_path)) - set(protos))
+    if unread:
+        raise P2RLibraryError(f"include/p2r_hip.h: the declarations of {unread} are outside the subset the binding reads")
+    return protos, structs
+
+
+_parsed = None
+
+
+def _header():
+    global _parsed
+    if _parsed is None:
+        _parsed = _parse(HEADER_PATH)
+    return _parsed
+
+
+def prototypes(header_path=None):
+    """name -> Prototype of every entry point the header declares."""
+    return _header()[0] if header_path is None else _parse(header_path)[0]
+
+
+def struct(name):
+    """The ctypes.Structure of the header's `typedef struct { ... } name;` (a field named like a Python keyword gets a
+    trailing underscore: p2r_pw_rjob.in is `in_`)."""
+    return _header()[1][name]
 
 
 def lib():
@@ -43,16 +156,12 @@ def lib():
         except OSError as e:  # pragma: no cover
             raise P2RLibraryError(f"cannot load {LIB_PATH}: {e}") from e
         l.p2r_abi_version.restype = ctypes.c_int
-        l.p2r_build_arch.restype = ctypes.c_char_p
         if l.p2r_abi_version() != ABI_VERSION:
             raise P2RLibraryError(f"libp2r_hip.so ABI version {l.p2r_abi_version()} != {ABI_VERSION}: stale library, rebuild it "
                                   "(make -C pose2room_amd/csrc)")
-        for name in declared_symbols():
+        for name, proto in prototypes().items():
             fn = getattr(l, name)
-            if name in ("p2r_stgcn_gcn3_signature", "p2r_stgcn_gcn3h_signature", "p2r_stgcn_gcn3h_weight_grad_signature"):
-                fn.restype = ctypes.c_uint64
-            elif name not in ("p2r_build_arch",):
-                fn.restype = ctypes.c_int
+            fn.restype, fn.argtypes = proto.restype, proto.argtypes
         _lib = l
     return _lib
 
@@ -72,6 +181,69 @@ def current_stream(device):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+# ---- launches -------------------------------------------------------------------------------------------------------------
+# what a pointer parameter takes besides a tensor and None: an address, a host array (job lists, counts), byref(struct)
+_HOST_POINTERS = (int, ctypes.c_void_p, ctypes.Array, type(ctypes.byref(ctypes.c_int())))
+
+
+def _address(proto, i, a):
+    if hasattr(a, "data_ptr"):
+        return a.data_ptr()
+    if not isinstance(a, _HOST_POINTERS):
+        raise TypeError(f"{proto.name}: argument {i} = {a!r} where a pointer is declared: {proto.text}")
+    return a
+
+
+def _scalar(proto, i, a):
+    if proto.kinds[i] == "i":
+        if not isinstance(a, numbers.Integral):
+            raise TypeError(f"{proto.name}: argument {i} = {a!r} where an integer is declared: {proto.text}")
+        return int(a)
+    if not isinstance(a, numbers.Real):
+        raise TypeError(f"{proto.name}: argument {i} = {a!r} where a float or double is declared: {proto.text}")
+    return float(a)
+
+
+def marshal(name, args):
+    """`args` = the parameters of entry point `name` in header order, without the trailing stream -> the list that goes
+    to the library: tensors as their address, None as NULL, integers as Python ints.  Raises TypeError unless the count
+    is exact (ctypes accepts surplus arguments) and every argument is of its parameter's kind.  Needs no GPU."""
+    proto = _header()[0].get(name)
+    if proto is None:
+        raise P2RLibraryError(f"{name} is not declared in include/p2r_hip.h")
+    if len(args) != len(proto.pointer):
+        raise TypeError(f"{name}: {len(args)} arguments for {len(proto.pointer)} parameters"
+                        f"{' in front of the stream' if proto.has_stream else ''}: {proto.text}")
+    try:        # the common case in one pass: every pointer a tensor or None
+        out = [a.data_ptr() if p and a is not None else a for a, p in zip(args, proto.pointer)]
+    except AttributeError:      # host arrays (job lists, counts), byref(struct), plain addresses
+        out = [_address(proto, i, a) if p and a is not None else a for i, (a, p) in enumerate(zip(args, proto.pointer))]
+    for i in proto.scalars:
+        if type(out[i]) is not int:
+            out[i] = _scalar(proto, i, out[i])
+    return out
+
+
+def launch_on(name, stream, *args):
+    """Entry point `name` on `stream` (what `current_stream` returns), for a block of launches under one device guard
+    and one stream lookup, both the caller's.  The entry point is looked up at every call: bench.py and the tests
+    replace attributes of the library object to time or trap launches."""
+    if not _header()[0][name].has_stream:
+        raise TypeError(f"{name} takes no stream: call lib().{name} directly")
+    check(getattr(lib(), name)(*marshal(name, args), stream), name)
+
+
+def launch(name, device, *args):
+    """One launch of entry point `name` on the current stream of `device`, made current for the call; `args` as for
+    `marshal`.  Raises when the library returns a non-zero status."""
+    import torch
+    if device.index is None or device.index == torch.cuda.current_device():
+        launch_on(name, current_stream(device), *args)      # `device` is current already: a guard would change nothing
+    else:
+        with torch.cuda.device(device):
+            launch_on(name, current_stream(device), *args)
+
+
 def sum_leading(part, tr64=False):
     """part [P, ...] f32 (kernel partials, one row per workgroup) -> part.sum(0), optionally with every trailing
     64 x 64 block transposed; one streaming launch (csrc/bn_act.hip: p2r_sum_leading)."""
@@ -83,7 +255,5 @@ def sum_leading(part, tr64=False):
         out = part.sum(0)
         return out.transpose(-1, -2).contiguous() if tr64 else out
     out = torch.empty(part.shape[1:], dtype=torch.float32, device=part.device)
-    with torch.cuda.device(part.device):
-        check(lib().p2r_sum_leading(P, ctypes.c_longlong(M), ptr(part), ptr(out), int(bool(tr64)),
-                                    current_stream(part.device)), "sum_leading")
+    launch("p2r_sum_leading", part.device, P, M, part, out, int(bool(tr64)))
     return out

@@ -10,8 +10,6 @@ device-resident form used by the eval path: B box sets in one launch, returning
 the keep mask without leaving the GPU (the reference loops over the batch on the
 host, net_utils/ap_helper.py:216-232).  No CPU fallback.
 """
-import ctypes
-
 import numpy as np
 import torch
 
@@ -35,12 +33,8 @@ def nms_3d_batched(boxes, overlap_threshold, old_type=False, same_cls=False, val
     keep = torch.zeros((B, K), dtype=torch.uint8, device=dev)
     pick = torch.full((B, K), -1, dtype=torch.int32, device=dev) if return_pick else None
     npick = torch.zeros((B,), dtype=torch.int32, device=dev) if return_pick else None
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().p2r_nms3d(
-            ctypes.c_int(B), ctypes.c_int(K), ctypes.c_int(stride), _lib.ptr(boxes), _lib.ptr(v),
-            ctypes.c_double(overlap_threshold), ctypes.c_int(int(old_type)),
-            ctypes.c_int(int(same_cls)), _lib.ptr(keep), _lib.ptr(pick), _lib.ptr(npick),
-            _lib.current_stream(dev)), "nms3d")
+    _lib.launch("p2r_nms3d", dev, B, K, stride, boxes, v, overlap_threshold, int(old_type), int(same_cls), keep, pick,
+                npick)
     if return_pick:
         return keep, pick, npick
     return keep

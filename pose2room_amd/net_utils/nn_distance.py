@@ -9,8 +9,6 @@ The reference materialises (B,N,M,C) intermediates with `repeat`; here forward
 and backward are one HIP launch each (pose2room_amd/csrc/nn_distance.hip) and
 nothing of size N*M touches HBM.  CUDA/HIP tensors only -- no CPU fallback.
 """
-import ctypes
-
 import torch
 from torch.autograd import Function
 
@@ -45,12 +43,7 @@ class _NNDistance(Function):
         idx1 = torch.empty((B, N), dtype=torch.int64, device=dev)
         dist2 = torch.empty((B, M), dtype=torch.float32, device=dev)
         idx2 = torch.empty((B, M), dtype=torch.int64, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().p2r_nn_distance(
-                ctypes.c_int(B), ctypes.c_int(N), ctypes.c_int(M), ctypes.c_int(C), _lib.ptr(a),
-                _lib.ptr(q), ctypes.c_int(mode), ctypes.c_float(delta), _lib.ptr(dist1),
-                _lib.ptr(idx1), _lib.ptr(dist2), _lib.ptr(idx2), _lib.current_stream(dev)),
-                "nn_distance")
+        _lib.launch("p2r_nn_distance", dev, B, N, M, C, a, q, mode, delta, dist1, idx1, dist2, idx2)
         ctx.save_for_backward(a, q, idx1, idx2)
         ctx.mode, ctx.delta = mode, delta
         ctx.mark_non_differentiable(idx1, idx2)
@@ -65,12 +58,7 @@ class _NNDistance(Function):
         g2 = g2.contiguous().float() if g2 is not None else None
         ga = torch.empty_like(a)
         gq = torch.empty_like(q)
-        with torch.cuda.device(a.device):
-            _lib.check(_lib.lib().p2r_nn_distance_grad(
-                ctypes.c_int(B), ctypes.c_int(N), ctypes.c_int(M), ctypes.c_int(C), _lib.ptr(a),
-                _lib.ptr(q), ctypes.c_int(ctx.mode), ctypes.c_float(ctx.delta), _lib.ptr(idx1),
-                _lib.ptr(idx2), _lib.ptr(g1), _lib.ptr(g2), _lib.ptr(ga), _lib.ptr(gq),
-                _lib.current_stream(a.device)), "nn_distance_grad")
+        _lib.launch("p2r_nn_distance_grad", a.device, B, N, M, C, a, q, ctx.mode, ctx.delta, idx1, idx2, g1, g2, ga, gq)
         return ga, gq, None, None
 
 

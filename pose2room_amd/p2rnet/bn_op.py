@@ -6,8 +6,6 @@ mode (batch statistics, running-stat update with the module's momentum, unbiased
 variance) and eval mode (running statistics), differentiable w.r.t. x, bn.weight, bn.bias
 and res.
 """
-import ctypes
-
 import torch
 from torch.autograd import Function
 
@@ -25,9 +23,7 @@ def _stats_partial(x):
     """per-(sample, channel) (count, mean, M2) rows [N, C, 3] from one HBM pass (see `moments`)."""
     N, C, L = _rows(x)
     part = torch.empty((N, C, 3), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().p2r_bn_stats(N * C, L, _lib.ptr(x), _lib.ptr(part), _lib.current_stream(x.device)),
-                   "bn_stats")
+    _lib.launch("p2r_bn_stats", x.device, N * C, L, x, part)
     return part
 
 
@@ -48,12 +44,8 @@ def finalize(part, M, bn):
         mom = 1.0 / float(bn.num_batches_tracked + 1)
     else:
         mom = float(bn.momentum)
-    with torch.cuda.device(part.device):
-        _lib.check(_lib.lib().p2r_bn_finalize(P, C, width, _lib.ptr(part), ctypes.c_double(float(M)), _lib.ptr(bn.weight),
-                                              _lib.ptr(bn.bias), ctypes.c_double(float(bn.eps)), ctypes.c_double(mom),
-                                              _lib.ptr(bn.running_mean), _lib.ptr(bn.running_var),
-                                              _lib.ptr(bn.num_batches_tracked), _lib.ptr(fin),
-                                              _lib.current_stream(part.device)), "bn_finalize")
+    _lib.launch("p2r_bn_finalize", part.device, P, C, width, part, float(M), bn.weight, bn.bias, float(bn.eps), mom,
+                bn.running_mean, bn.running_var, bn.num_batches_tracked, fin)
     return fin
 
 
@@ -62,9 +54,7 @@ def bwd_finalize(part, M):
     part = part.contiguous()
     P, C = part.shape[0], part.shape[1]
     out = torch.empty((4, C), dtype=torch.float32, device=part.device)
-    with torch.cuda.device(part.device):
-        _lib.check(_lib.lib().p2r_bn_bwd_finalize(P, C, _lib.ptr(part), ctypes.c_double(float(M)), _lib.ptr(out),
-                                                  _lib.current_stream(part.device)), "bn_bwd_finalize")
+    _lib.launch("p2r_bn_bwd_finalize", part.device, P, C, part, float(M), out)
     return out
 
 
@@ -92,18 +82,13 @@ def _apply(x, scale, shift, res, relu, want_mask=False):
     N, C, L = _rows(x)
     y = torch.empty_like(x)
     mask = torch.empty(x.shape, dtype=torch.uint8, device=x.device) if (want_mask and relu) else None
-    with torch.cuda.device(x.device):
-        if relu and want_mask and math_mode.split16() and x.dim() == 4 and N > 0:
-            # split16 mode: y is (typically) the next block's graph-conv input -- its range word leaves with it
-            word = math_mode.new_word(x.device)
-            _lib.check(_lib.lib().p2r_bn_apply_amax(N, C, L, _lib.ptr(x), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(res),
-                                                    _lib.ptr(y), _lib.ptr(mask), _lib.ptr(word),
-                                                    _lib.current_stream(x.device)), "bn_apply_amax")
-            math_mode.announce(y, word)
-        else:
-            _lib.check(_lib.lib().p2r_bn_apply(N, C, L, _lib.ptr(x), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(res),
-                                               int(relu), _lib.ptr(y), _lib.ptr(mask), _lib.current_stream(x.device)),
-                       "bn_apply")
+    if relu and want_mask and math_mode.split16() and x.dim() == 4 and N > 0:
+        # split16 mode: y is (typically) the next block's graph-conv input -- its range word leaves with it
+        word = math_mode.new_word(x.device)
+        _lib.launch("p2r_bn_apply_amax", x.device, N, C, L, x, scale, shift, res, y, mask, word)
+        math_mode.announce(y, word)
+    else:
+        _lib.launch("p2r_bn_apply", x.device, N, C, L, x, scale, shift, res, int(relu), y, mask)
     return (y, mask) if want_mask else y
 
 
@@ -192,7 +177,6 @@ class _FusedBNAct(Function):
         dy = dy.contiguous()
         N, C, L = _rows(x)
         dev = x.device
-        lib = _lib.lib()
         link, part, ready = ctx.link, None, None
         sums = handoff.take(dy, 'bn_sums') if link is not None else None
         if sums is not None and sums[0] is link:
@@ -205,10 +189,7 @@ class _FusedBNAct(Function):
 
         def reduce_pass():
             part_ = torch.empty((N, C, 2), dtype=torch.float32, device=dev)
-            with torch.cuda.device(dev):
-                _lib.check(lib.p2r_bn_bwd_reduce(N, C, L, _lib.ptr(dy), _lib.ptr(mask), _lib.ptr(x), _lib.ptr(mean),
-                                                 _lib.ptr(invstd), mode, None, None, _lib.ptr(part_),
-                                                 _lib.current_stream(dev)), "bn_bwd_reduce")
+            _lib.launch("p2r_bn_bwd_reduce", dev, N, C, L, dy, mask, x, mean, invstd, mode, None, None, part_)
             return part_
 
         if part is None and not side_ok:
@@ -220,19 +201,14 @@ class _FusedBNAct(Function):
             dx_ = torch.empty_like(x)
             dres_ = torch.empty_like(x) if (ctx.has_res and not ctx.lazy_res) else None
             word_ = math_mode.new_word(dev) if ctx.split else None
-            with torch.cuda.device(dev):
-                if word_ is not None:
-                    # split16 mode: dx is the incoming gradient of the temporal conv's data-gradient kernel
-                    _lib.check(lib.p2r_bn_bwd_apply_amax(N, C, L, _lib.ptr(dy), _lib.ptr(mask), _lib.ptr(x), _lib.ptr(mean),
-                                                         _lib.ptr(invstd), _lib.ptr(kscale), _lib.ptr(tot_[2]),
-                                                         _lib.ptr(tot_[3]), _lib.ptr(dx_), _lib.ptr(dres_), _lib.ptr(word_),
-                                                         _lib.current_stream(dev)), "bn_bwd_apply_amax")
-                    math_mode.announce(dx_, word_)
-                else:
-                    _lib.check(lib.p2r_bn_bwd_apply(N, C, L, _lib.ptr(dy), _lib.ptr(mask), _lib.ptr(x), _lib.ptr(mean),
-                                                    _lib.ptr(invstd), _lib.ptr(kscale), _lib.ptr(tot_[2]), _lib.ptr(tot_[3]),
-                                                    mode, None, None, _lib.ptr(dx_), _lib.ptr(dres_),
-                                                    _lib.current_stream(dev)), "bn_bwd_apply")
+            if word_ is not None:
+                # split16 mode: dx is the incoming gradient of the temporal conv's data-gradient kernel
+                _lib.launch("p2r_bn_bwd_apply_amax", dev, N, C, L, dy, mask, x, mean, invstd, kscale, tot_[2], tot_[3], dx_,
+                            dres_, word_)
+                math_mode.announce(dx_, word_)
+            else:
+                _lib.launch("p2r_bn_bwd_apply", dev, N, C, L, dy, mask, x, mean, invstd, kscale, tot_[2], tot_[3], mode,
+                            None, None, dx_, dres_)
             return tot_, dx_, dres_, word_
 
         if side_ok and SIDE_INLINE:

@@ -241,15 +241,7 @@ class DeviceSampleStore(object):
         return out
 
 
-class _Store(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_void_p) for n in ('joints', 'votes', 'frame_offset', 'n_frames', 'floor_height',
-                                               'box_center', 'box_heading', 'box_size', 'box_mask', 'box_cls')] + \
-               [('n_frames_total', ctypes.c_longlong)] + [(n, ctypes.c_int) for n in ('n_samples', 'J', 'K')]
-
-
-class _Out(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_void_p) for n in ('input_joints', 'vote_label', 'vote_label_mask', 'center_label', 'size',
-                                               'heading', 'box_label_mask', 'sem_cls_label')]
+_Store, _Out = _lib.struct('p2r_sample_store'), _lib.struct('p2r_batch_out')
 
 
 def assemble_batch(store, sel, aug, augment, use_height, num_frames, out):
@@ -262,11 +254,8 @@ def assemble_batch(store, sel, aug, augment, use_height, num_frames, out):
             (aug is not None and (aug.dtype != torch.float64 or aug.shape != (sel.shape[0], 10))):
         raise RuntimeError("assemble_batch: sel (B, 3) int64 and aug (B, 10) float64 expected")
     o = _Out(**{f[0]: out[f[0]].data_ptr() for f in _Out._fields_})
-    with torch.cuda.device(store.device):
-        _lib.check(_lib.lib().p2r_assemble_batch(ctypes.byref(store._c), int(sel.shape[0]), _lib.ptr(sel),
-                                                 _lib.ptr(aug), int(bool(augment)), int(bool(use_height)),
-                                                 int(num_frames), ctypes.byref(o), _lib.current_stream(store.device)),
-                   "assemble_batch")
+    _lib.launch("p2r_assemble_batch", store.device, ctypes.byref(store._c), int(sel.shape[0]), sel, aug, int(bool(augment)),
+                int(bool(use_height)), int(num_frames), ctypes.byref(o))
     return out
 
 

@@ -77,11 +77,8 @@ class _EmbedMLP(Function):
             if (tconv_op.USE_GEN3 and inner == 53 and rows % 16 == 0 and add_c.shape == (B, 64, rows)
                     and z2.data_ptr() % 16 == 0):
                 out = torch.empty_like(z2)
-                with torch.cuda.device(dev):
-                    _lib.check(_lib.lib().p2r_stgcn_tconv3_forward_add(
-                        B, rows, inner, _lib.ptr(z2), _lib.ptr(fin2[2]), _lib.ptr(fin2[3]),
-                        _lib.ptr(tconv_op._permute_taps(W2)), _lib.ptr(bias2), _lib.ptr(add_c), _lib.ptr(out),
-                        _lib.current_stream(dev)), "stgcn_tconv3_forward_add")
+                _lib.launch("p2r_stgcn_tconv3_forward_add", dev, B, rows, inner, z2, fin2[2], fin2[3],
+                            tconv_op._permute_taps(W2), bias2, add_c, out)
         if out is None:
             out = tconv_op._tconv(z2, fin2[2], fin2[3], W2, bias2)
             if add_ct is not None:
@@ -102,7 +99,6 @@ class _EmbedMLP(Function):
         f32 = dict(dtype=torch.float32, device=dev)
         du = dout.contiguous()
         P = _N_BLOCKS
-        lib = _lib.lib()
         g2, g1 = torch.empty((B, 64, L), **f32), torch.empty((B, 64, L), **f32)
         sum2, sum1 = torch.empty((P, 64, 2), **f32), torch.empty((P, 64, 2), **f32)
         dw2p, dw1p = torch.empty((P, 64, 64), **f32), torch.empty((P, 64, 64), **f32)
@@ -117,16 +113,11 @@ class _EmbedMLP(Function):
             if has_add and ctx.needs_input_grad[1]:
                 from . import seed_op
                 d_add = seed_op._rowsum(du.view(B, 64, L // inner, inner), inner, 1.0)
-            _lib.check(lib.p2r_embed_layer_backward(B, L, _lib.ptr(du), None, None, _lib.ptr(z2), _lib.ptr(fin2),
-                                                    _lib.ptr(W2m), _lib.ptr(g2), _lib.ptr(sum2), P, _lib.ptr(dw2p),
-                                                    _lib.ptr(db2p), st), "embed_layer_backward")
+            _lib.launch_on("p2r_embed_layer_backward", st, B, L, du, None, None, z2, fin2, W2m, g2, sum2, P, dw2p, db2p)
             (dg1, dbe1), = pw_op._bn_bwd_finalize([sum2], fin2, coef2, [0], [64], B * L, train, st)
-            _lib.check(lib.p2r_embed_layer_backward(B, L, _lib.ptr(g2), _lib.ptr(z2), _lib.ptr(coef2), _lib.ptr(z1),
-                                                    _lib.ptr(fin1), _lib.ptr(W1m), _lib.ptr(g1), _lib.ptr(sum1), P,
-                                                    _lib.ptr(dw1p), _lib.ptr(db1p), st), "embed_layer_backward")
+            _lib.launch_on("p2r_embed_layer_backward", st, B, L, g2, z2, coef2, z1, fin1, W1m, g1, sum1, P, dw1p, db1p)
             (dg0, dbe0), = pw_op._bn_bwd_finalize([sum1], fin1, coef1, [0], [64], B * L, train, st)
-            _lib.check(lib.p2r_embed3_weight_grad_lazy(B, L, _lib.ptr(x), _lib.ptr(g1), _lib.ptr(z1), _lib.ptr(coef1),
-                                                       _lib.ptr(w0p), st), "embed3_weight_grad_lazy")
+            _lib.launch_on("p2r_embed3_weight_grad_lazy", st, B, L, x, g1, z1, coef1, w0p)
             dW2, dW1 = torch.empty(w2.shape, **f32), torch.empty(w1.shape, **f32)
             w0g = torch.empty((64, 4), **f32)
             red = [(dw2p, dW2), (dw1p, dW1), (w0p, w0g)]

@@ -113,10 +113,7 @@ def _gcn_forward(x, W, nbr, coef, LkA, bias_cv, tables, want_stats=False):
     if want_stats:      # one (sum, sum of squares) row pair per workgroup = per (sample, tile of 384 // V frames)
         frames = min(384 // V, T)
         part = torch.empty((N * ((T + frames - 1) // frames), C, 2), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().p2r_stgcn_gcn_forward(
-            N, T, V, tables.K, LkA, _lib.ptr(x), _lib.ptr(W), _lib.ptr(nbr), _lib.ptr(coef),
-            _lib.ptr(bias_cv), _lib.ptr(z), _lib.ptr(part), _lib.current_stream(x.device)), "stgcn_gcn_forward")
+    _lib.launch("p2r_stgcn_gcn_forward", x.device, N, T, V, tables.K, LkA, x, W, nbr, coef, bias_cv, z, part)
     return (z, part) if want_stats else z
 
 
@@ -149,7 +146,6 @@ def _gcn2_forward(x, Wp, coef, stream, bias_cv, tables, want_stats=False, addend
     kernel then takes the launch if the tables carry the pattern it was generated for; `stream` is for gcn2."""
     N, C, T, V = x.shape
     z = torch.empty_like(x)
-    lib = _lib.lib()
     part = None
     ltot = coef.shape[0]
     with torch.cuda.device(x.device):
@@ -166,24 +162,18 @@ def _gcn2_forward(x, Wp, coef, stream, bias_cv, tables, want_stats=False, addend
                                dtype=torch.float32, device=x.device)
         if gen3 and addend_mask is not None:
             bu, bm, bf = (bwd[0], bwd[1], bwd[2].contiguous()) if bwd is not None else (None, None, None)
-            _lib.check(lib.p2r_stgcn_gcn3_data_gradient_masked_addend(
-                N, T, V, tables.K, ltot, _lib.ptr(x), _lib.ptr(Wp), _lib.ptr(coef), _lib.ptr(addend), _lib.ptr(addend_mask),
-                _lib.ptr(z), _lib.ptr(part), _lib.ptr(bu), _lib.ptr(bm), _lib.ptr(bf), st),
-                "stgcn_gcn3_data_gradient_masked_addend")
+            _lib.launch_on("p2r_stgcn_gcn3_data_gradient_masked_addend", st, N, T, V, tables.K, ltot, x, Wp, coef, addend,
+                           addend_mask, z, part, bu, bm, bf)
             return (z, part) if want_stats else z
         if gen3:
             bu, bm, bf = (bwd[0], bwd[1], bwd[2].contiguous()) if bwd is not None else (None, None, None)
-            _lib.check(lib.p2r_stgcn_gcn3_forward(N, T, V, tables.K, ltot, int(form), _lib.ptr(x), _lib.ptr(Wp),
-                                                  _lib.ptr(coef), _lib.ptr(bias_cv), _lib.ptr(addend), _lib.ptr(z),
-                                                  _lib.ptr(part), None, _lib.ptr(bu), _lib.ptr(bm), _lib.ptr(bf), st),
-                       "stgcn_gcn3_forward")
+            _lib.launch_on("p2r_stgcn_gcn3_forward", st, N, T, V, tables.K, ltot, int(form), x, Wp, coef, bias_cv, addend, z,
+                           part, None, bu, bm, bf)
             return (z, part) if want_stats else z
         work = torch.empty_like(stream)       # the stream with this call's coefficients (scalar-loaded by the kernel)
         bu, bm, bf = (bwd[0], bwd[1], bwd[2].contiguous()) if bwd is not None else (None, None, None)
-        _lib.check(lib.p2r_stgcn_gcn2_forward(N, T, V, tables.K, ltot, _lib.ptr(x), _lib.ptr(Wp), _lib.ptr(coef),
-                                              _lib.ptr(stream), _lib.ptr(work), _lib.ptr(bias_cv), _lib.ptr(addend),
-                                              _lib.ptr(z), _lib.ptr(part), None, _lib.ptr(bu), _lib.ptr(bm),
-                                              _lib.ptr(bf), st), "stgcn_gcn2_forward")
+        _lib.launch_on("p2r_stgcn_gcn2_forward", st, N, T, V, tables.K, ltot, x, Wp, coef, stream, work, bias_cv, addend, z,
+                       part, None, bu, bm, bf)
     return (z, part) if want_stats else z
 
 
@@ -277,22 +267,16 @@ def _gcn3h_forward(x, sp, coef, bias_cv, tables, want_stats, x_word):
     N, C, T, V = x.shape
     z = torch.empty_like(x)
     part = torch.empty((min(N * (T // 16), 256), C, 3), dtype=torch.float32, device=x.device) if want_stats else None
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().p2r_stgcn_gcn3h_forward(
-            N, T, V, tables.K, coef.shape[0], _lib.ptr(x), _lib.ptr(sp.wh), _lib.ptr(sp.winv), _lib.ptr(coef),
-            _lib.ptr(bias_cv), _lib.ptr(z), _lib.ptr(part), None, _lib.ptr(x_word), _lib.current_stream(x.device)),
-            "stgcn_gcn3h_forward")
+    _lib.launch("p2r_stgcn_gcn3h_forward", x.device, N, T, V, tables.K, coef.shape[0], x, sp.wh, sp.winv, coef, bias_cv, z,
+                part, None, x_word)
     return (z, part) if want_stats else z
 
 
 def _gcn3h_data_gradient(dz, sp, coef, tables, addend, addend_mask, dz_word):
     N, C, T, V = dz.shape
     dx = torch.empty_like(dz)
-    with torch.cuda.device(dz.device):
-        _lib.check(_lib.lib().p2r_stgcn_gcn3h_data_gradient(
-            N, T, V, tables.K, coef.shape[0], _lib.ptr(dz), _lib.ptr(sp.wh), _lib.ptr(sp.winv), _lib.ptr(coef),
-            _lib.ptr(addend), _lib.ptr(addend_mask), _lib.ptr(dx), _lib.ptr(dz_word), _lib.current_stream(dz.device)),
-            "stgcn_gcn3h_data_gradient")
+    _lib.launch("p2r_stgcn_gcn3h_data_gradient", dz.device, N, T, V, tables.K, coef.shape[0], dz, sp.wh, sp.winv, coef,
+                addend, addend_mask, dx, dz_word)
     return dx
 
 
@@ -398,7 +382,6 @@ class _GraphConv(Function):
                 ready = torch.cuda.Event()
                 ready.record(torch.cuda.current_stream(dev))
                 handoff.put(dx, 'bn_sums', (link, sums, ready))
-        lib = _lib.lib()
         st = _lib.current_stream(dev)
         with torch.cuda.device(dev):
             if ctx.needs_input_grad[1]:
@@ -410,21 +393,16 @@ class _GraphConv(Function):
                 bpart = torch.empty((_N_BLOCKS, C, V), dtype=torch.float32, device=dev) if ctx.needs_input_grad[4] else None
                 if ctx.split is not None and SPLIT_WEIGHT_GRAD and dz.data_ptr() % 16 == 0:
                     # split16 mode (csrc/stgcn_gcn3dwh.hip): both operands are runtime tensors, each with its range word
-                    _lib.check(lib.p2r_stgcn_gcn3h_weight_grad(
-                        N, T, V, K, coef_r.shape[0], _lib.ptr(x), _lib.ptr(dz), _lib.ptr(coef_r.contiguous()), _N_BLOCKS,
-                        _lib.ptr(part), _lib.ptr(bpart), _lib.ptr(ctx.x_word), _lib.ptr(dz_word), st),
-                        "stgcn_gcn3h_weight_grad")
+                    _lib.launch_on("p2r_stgcn_gcn3h_weight_grad", st, N, T, V, K, coef_r.shape[0], x, dz, coef_r.contiguous(),
+                                   _N_BLOCKS, part, bpart, ctx.x_word, dz_word)
                 elif (USE_GEN3 and tables.gen3 and N > 0 and T % 4 == 0 and x.data_ptr() % 16 == 0
                         and dz.data_ptr() % 16 == 0):      # (N == 0: the first-generation kernel returns zeros)
                     # statically scheduled kernel (csrc/stgcn_gcn3_dw.hip)
-                    _lib.check(lib.p2r_stgcn_gcn3_weight_grad(
-                        N, T, V, K, coef_r.shape[0], _lib.ptr(x), _lib.ptr(dz), _lib.ptr(coef_r.contiguous()), _N_BLOCKS,
-                        _lib.ptr(part), _lib.ptr(bpart), st), "stgcn_gcn3_weight_grad")
+                    _lib.launch_on("p2r_stgcn_gcn3_weight_grad", st, N, T, V, K, coef_r.shape[0], x, dz, coef_r.contiguous(),
+                                   _N_BLOCKS, part, bpart)
                 else:
-                    _lib.check(lib.p2r_stgcn_gcn_weight_grad(
-                        N, T, V, K, tables.LkA_r, _lib.ptr(dz), _lib.ptr(x), _lib.ptr(t['nbr_r']),
-                        _lib.ptr(coef_r.contiguous()), _N_BLOCKS, _lib.ptr(part), _lib.ptr(bpart), 1, st),
-                        "stgcn_gcn_weight_grad")
+                    _lib.launch_on("p2r_stgcn_gcn_weight_grad", st, N, T, V, K, tables.LkA_r, dz, x, t['nbr_r'],
+                                   coef_r.contiguous(), _N_BLOCKS, part, bpart, 1)
                 dW = _lib.sum_leading(part, tr64=True).reshape(K * C, C)      # the kernel returns dW_k^T
                 if bpart is not None:
                     dbias = _lib.sum_leading(bpart)                        # (C, V)
@@ -438,23 +416,20 @@ class _GraphConv(Function):
                         and x.data_ptr() % 16 == 0):
                     # split16 mode (csrc/stgcn_gcn3h_grad.hip): Y_k = W_k x on two-part fp16 operands; dz stays fp32
                     sp = ctx.split[2]
-                    _lib.check(lib.p2r_stgcn_gcn3h_coef_grad(N, T, V, K, ltot, _lib.ptr(x), _lib.ptr(dz), _lib.ptr(sp.wh),
-                                                             _lib.ptr(sp.winv), _N_BLOCKS, _lib.ptr(part),
-                                                             _lib.ptr(ctx.x_word), st), "stgcn_gcn3h_coef_grad")
+                    _lib.launch_on("p2r_stgcn_gcn3h_coef_grad", st, N, T, V, K, ltot, x, dz, sp.wh, sp.winv, _N_BLOCKS, part,
+                                   ctx.x_word)
                 elif USE_GEN3 and tables.gen3 and T % 16 == 0 and dz.data_ptr() % 16 == 0:
                     # statically scheduled kernel (csrc/stgcn_gcn3_grad.hip)
                     wp_f = ctx.wp_f if ctx.wp_f is not None else permute_planes(W.view(K, C, C))
-                    _lib.check(lib.p2r_stgcn_gcn3_coef_grad(N, T, V, K, ltot, _lib.ptr(x), _lib.ptr(dz), _lib.ptr(wp_f),
-                                                            _N_BLOCKS, _lib.ptr(part), st), "stgcn_gcn3_coef_grad")
+                    _lib.launch_on("p2r_stgcn_gcn3_coef_grad", st, N, T, V, K, ltot, x, dz, wp_f, _N_BLOCKS, part)
                 else:
-                    _lib.check(lib.p2r_stgcn_gcn_coef_grad(
-                        N, T, V, K, tables.LkA_r, _lib.ptr(dz), _lib.ptr(x), _lib.ptr(W), _lib.ptr(t['nbr_r']),
-                        _lib.ptr(t['real_r']), _N_BLOCKS, _lib.ptr(part), st), "stgcn_gcn_coef_grad")
+                    _lib.launch_on("p2r_stgcn_gcn_coef_grad", st, N, T, V, K, tables.LkA_r, dz, x, W, t['nbr_r'], t['real_r'],
+                                   _N_BLOCKS, part)
                 dcoef_r = _lib.sum_leading(part)
         if ctx.needs_input_grad[4] and dbias is None:
             part = torch.empty((N * C, V), dtype=torch.float32, device=dev)
             with torch.cuda.device(dev):
-                _lib.check(lib.p2r_colsum(N * C, T, V, _lib.ptr(dz), _lib.ptr(part), st), "colsum")
+                _lib.launch_on("p2r_colsum", st, N * C, T, V, dz, part)
             dbias = part.view(N, C, V).sum(0)                          # (C, V)
         if dres is not None:
             if dres_mask is not None:

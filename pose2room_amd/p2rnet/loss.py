@@ -13,8 +13,6 @@ runs over the valid rows only.  `object_assignment` therefore indexes the UNcomp
 which equals the reference's index whenever `box_label_mask` is a prefix of ones -- the form
 the reference loader produces (dataloader.py:113-121) and `synthetic.make_batch` keeps.
 """
-import ctypes
-
 import torch
 from torch import nn
 from torch.autograd import Function
@@ -244,16 +242,10 @@ class _DetectionLoss(Function):
                                             'heading', 'sem_cls_label')]
         if gts[1].dtype != torch.int64 or gts[6].dtype != torch.int64:
             raise RuntimeError("det_loss: vote_label_mask and sem_cls_label must be int64")
-        c = ctypes.c_float
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().p2r_det_loss_forward(
-                B, S, J, T, K, G, NC, int(j0), c(NEAR_THRESHOLD), c(FAR_THRESHOLD), c(OBJECTNESS_CLS_WEIGHTS[0]),
-                c(OBJECTNESS_CLS_WEIGHTS[1]), _lib.ptr(seed_skeleton), _lib.ptr(vote_xyz), _lib.ptr(seed_inds),
-                _lib.ptr(gts[0]), _lib.ptr(gts[1]), _lib.ptr(agg_xyz), _lib.ptr(center), _lib.ptr(size),
-                _lib.ptr(heading), _lib.ptr(obj_scores), _lib.ptr(sem_scores), _lib.ptr(gts[2]), _lib.ptr(gts[3]),
-                _lib.ptr(gts[4]), _lib.ptr(gts[5]), _lib.ptr(gts[6]), _lib.ptr(part), _lib.ptr(part64),
-                _lib.ptr(out32), _lib.ptr(out64), _lib.ptr(g_vote), _lib.ptr(g_obj), _lib.ptr(g_c1), _lib.ptr(g_c2),
-                _lib.ptr(g_size), _lib.ptr(g_head), _lib.ptr(g_sem), _lib.current_stream(dev)), "det_loss_forward")
+        _lib.launch("p2r_det_loss_forward", dev, B, S, J, T, K, G, NC, int(j0), NEAR_THRESHOLD, FAR_THRESHOLD,
+                    OBJECTNESS_CLS_WEIGHTS[0], OBJECTNESS_CLS_WEIGHTS[1], seed_skeleton, vote_xyz, seed_inds, gts[0], gts[1],
+                    agg_xyz, center, size, heading, obj_scores, sem_scores, gts[2], gts[3], gts[4], gts[5], gts[6], part,
+                    part64, out32, out64, g_vote, g_obj, g_c1, g_c2, g_size, g_head, g_sem)
         ctx.save_for_backward(out32, g_vote, g_obj, g_c1, g_c2, g_size, g_head, g_sem)
         ctx.set_materialize_grads(False)      # unused loss terms arrive as None, not as zero tensors
         ctx.dims = (B, S, K, NC)
@@ -279,12 +271,8 @@ class _DetectionLoss(Function):
         o_obj, o_center, o_size = (torch.empty((B, K, d), **f32) for d in (2, 3, 3))
         o_head = torch.empty((B, K, 2), dtype=torch.float64, device=dev)
         o_sem = torch.empty((B, K, NC), **f32)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().p2r_det_loss_backward(
-                B, S, K, NC, _lib.ptr(coef), _lib.ptr(out32), _lib.ptr(g_vote), _lib.ptr(g_obj), _lib.ptr(g_c1),
-                _lib.ptr(g_c2), _lib.ptr(g_size), _lib.ptr(g_head), _lib.ptr(g_sem), _lib.ptr(o_vote), _lib.ptr(o_obj),
-                _lib.ptr(o_center), _lib.ptr(o_size), _lib.ptr(o_head), _lib.ptr(o_sem), _lib.current_stream(dev)),
-                "det_loss_backward")
+        _lib.launch("p2r_det_loss_backward", dev, B, S, K, NC, coef, out32, g_vote, g_obj, g_c1, g_c2, g_size, g_head, g_sem,
+                    o_vote, o_obj, o_center, o_size, o_head, o_sem)
         return o_vote, o_obj, o_center, o_size, o_head, o_sem, None, None, None, None, None
 
 

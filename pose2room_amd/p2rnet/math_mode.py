@@ -16,7 +16,6 @@ leaves that maximum as one uint32 in device memory on the tensor itself (`announ
 up there (`range_word`), or computes it with one extra read of the tensor when nobody announced it.
 """
 import contextlib
-import ctypes
 import os
 
 import torch
@@ -76,9 +75,7 @@ def range_word(t, keep=False):
     if word is not None:
         return word
     word = new_word(t.device)
-    with torch.cuda.device(t.device):
-        _lib.check(_lib.lib().p2r_absmax_bits(ctypes.c_longlong(t.numel()), _lib.ptr(t), _lib.ptr(word),
-                                              _lib.current_stream(t.device)), "absmax_bits")
+    _lib.launch("p2r_absmax_bits", t.device, t.numel(), t, word)
     FALLBACK_PASSES += 1
     return word
 

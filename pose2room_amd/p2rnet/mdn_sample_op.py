@@ -20,9 +20,6 @@ import torch
 
 from .. import _lib
 
-_P = ctypes.c_void_p
-_I = ctypes.c_int
-
 PHILOX_M = (0xD2511F53, 0xCD9E8D57)
 PHILOX_W = (0x9E3779B9, 0xBB67AE85)
 MAX_HEADS, MAX_G, MAX_D, MAX_N = 3, 256, 4, 256
@@ -31,12 +28,7 @@ MAX_HEADS, MAX_G, MAX_D, MAX_N = 3, 256, 4, 256
 READOUTS = {'mean': 0, 'median': 1}
 
 
-class _SampleHead(ctypes.Structure):
-    _fields_ = [(n, _P) for n in ('pi', 'log_sigma', 'mu', 'out')] + [(n, _I) for n in ('D', 'f64', 'head_id')]
-
-
-class _SampleHeadEx(ctypes.Structure):
-    _fields_ = [(n, _P) for n in ('pi', 'log_sigma', 'mu', 'out', 'draws')] + [(n, _I) for n in ('D', 'f64', 'head_id')]
+_SampleHead, _SampleHeadEx = _lib.struct('p2r_mdn_sample_head'), _lib.struct('p2r_mdn_sample_head_ex')
 
 
 def readout_code(readout):
@@ -91,22 +83,19 @@ def sample(heads, pis, n_samples, seed, h_offset=0, head_ids=None, readout='mean
         out = torch.empty((H, B, L, D), dtype=mu.dtype, device=dev)
         keep += [mu, ls]
         outs.append(out)
-        fields = dict(pi=_lib.ptr(p), log_sigma=_lib.ptr(ls), mu=_lib.ptr(mu), out=_lib.ptr(out), D=D,
+        fields = dict(pi=p.data_ptr(), log_sigma=ls.data_ptr(), mu=mu.data_ptr(), out=out.data_ptr(), D=D,
                       f64=int(mu.dtype == torch.float64), head_id=head_ids[i])
         if return_draws:
             draws.append(torch.empty((H, B, L, n_max, D), dtype=mu.dtype, device=dev))
-            fields['draws'] = _lib.ptr(draws[-1])
+            fields['draws'] = draws[-1].data_ptr()
         hs.append(_SampleHeadEx(**fields) if ex else _SampleHead(**fields))
     arr = (type(hs[0]) * len(hs))(*hs)
     narr = (ctypes.c_int * H)(*ns)
-    key = ctypes.c_ulonglong(int(seed) & 0xffffffffffffffff)
-    with torch.cuda.device(dev):
-        if ex:
-            _lib.check(_lib.lib().p2r_mdn_sample_ex(len(hs), arr, B, G, L, ctot, H, narr, key, int(h_offset), code, n_max,
-                                                    _lib.current_stream(dev)), "mdn_sample_ex")
-        else:
-            _lib.check(_lib.lib().p2r_mdn_sample(len(hs), arr, B, G, L, ctot, H, narr, key, int(h_offset),
-                                                 _lib.current_stream(dev)), "mdn_sample")
+    key = int(seed) & 0xffffffffffffffff
+    if ex:
+        _lib.launch('p2r_mdn_sample_ex', dev, len(hs), arr, B, G, L, ctot, H, narr, key, int(h_offset), code, n_max)
+    else:
+        _lib.launch('p2r_mdn_sample', dev, len(hs), arr, B, G, L, ctot, H, narr, key, int(h_offset))
     return (outs, draws) if return_draws else outs
 
 

@@ -12,48 +12,14 @@ the proposal head is 10 launches forward and 15 backward instead of ~115 / ~230 
 5 and 9 instead of ~20 / ~60.  The BatchNorm + ReLU between two layers is applied by the consumer while it stages its
 input tile; pre-BatchNorm gradients exist only as (masked gradient, saved conv output, three constants per channel).
 """
-import ctypes
-
 import torch
 from torch.autograd import Function
 
 from .. import _lib
 from . import bn_op
 
-_P = ctypes.c_void_p
-_I = ctypes.c_int
-
-
-class _Job(ctypes.Structure):
-    _fields_ = [(n, _P) for n in ('x', 'x2', 'tr', 'w', 'bias', 'mz', 'mfin', 'out', 'stats')] + \
-               [(n, _I) for n in ('k', 'rows', 'x_ctot', 'x_nlc', 'tr_mode', 'tr_ld', 'w_t', 'out_ctot', 'out_nlc',
-                                  'epilogue', 'mz_ctot', 'mfin_ld')]
-
-
-class _WJob(ctypes.Structure):
-    _fields_ = [(n, _P) for n in ('x', 'x2', 'tr', 'y', 'ytr', 'dw_part', 'db_part')] + \
-               [(n, _I) for n in ('rows', 'k', 'x_ctot', 'x_nlc', 'tr_mode', 'tr_ld', 'y_ctot', 'y_nlc', 'ytr_ld',
-                                  'split')]
-
-
-class _BnJob(ctypes.Structure):
-    _fields_ = [(n, _P) for n in ('part', 'gamma', 'beta', 'running_mean', 'running_var', 'fin',
-                                  'num_batches_tracked')] + \
-               [('eps', ctypes.c_double), ('momentum', ctypes.c_double)] + [(n, _I) for n in ('P', 'C', 'fin_ld')]
-
-
-class _BnbJob(ctypes.Structure):
-    _fields_ = [(n, _P) for n in ('part', 'fin', 'coef', 'dgamma', 'dbeta')] + [('M', ctypes.c_double)] + \
-               [(n, _I) for n in ('P', 'C', 'fin_ld', 'coef_ld', 'train')]
-
-
-class _RJob(ctypes.Structure):
-    _fields_ = [('in_', _P), ('out', _P), ('P', _I), ('M', _I)]
-
-
-class _MixHead(ctypes.Structure):
-    _fields_ = [(n, _P) for n in ('logit', 'log_sigma', 'mu', 'eps', 'dpred', 'pred', 'dmu', 'pi', 'dlogit',
-                                  'dlog_sigma')] + [('D', _I), ('f64', _I)]
+_Job, _WJob, _BnJob, _BnbJob = (_lib.struct(n) for n in ('p2r_pw_job', 'p2r_pw_wjob', 'p2r_pw_bnjob', 'p2r_pw_bnbjob'))
+_RJob, _MixHead = _lib.struct('p2r_pw_rjob'), _lib.struct('p2r_mix_head')
 
 
 def _at(t, off=0):
@@ -63,9 +29,9 @@ def _at(t, off=0):
     return t.data_ptr() + off * t.element_size()
 
 
-def _launch(fn_name, struct, jobs, *tail):
+def _launch(fn_name, struct, jobs, st, *dims):
     arr = (struct * len(jobs))(*[struct(**j) for j in jobs])
-    _lib.check(getattr(_lib.lib(), fn_name)(len(jobs), arr, *tail), fn_name)
+    _lib.launch_on(fn_name, st, len(jobs), arr, *dims)
 
 
 def _gemm(jobs, B, L, st):
@@ -74,7 +40,7 @@ def _gemm(jobs, B, L, st):
                      ('x_nlc', 0), ('tr_mode', 0), ('tr_ld', 0), ('w_t', 0), ('out_nlc', 0), ('epilogue', 0),
                      ('mz_ctot', 0), ('mfin_ld', 0)):
             j.setdefault(k, v)
-    _launch('p2r_pw_gemm', _Job, jobs, B, L, st)
+    _launch('p2r_pw_gemm', _Job, jobs, st, B, L)
 
 
 def _wgrad(jobs, B, L, st):
@@ -82,7 +48,7 @@ def _wgrad(jobs, B, L, st):
         for k, v in (('x2', None), ('tr', None), ('ytr', None), ('db_part', None), ('x_nlc', 0), ('tr_mode', 0),
                      ('tr_ld', 0), ('y_nlc', 0), ('ytr_ld', 0)):
             j.setdefault(k, v)
-    _launch('p2r_pw_wgrad', _WJob, jobs, B, L, st)
+    _launch('p2r_pw_wgrad', _WJob, jobs, st, B, L)
 
 
 def _reduce(jobs, st):
@@ -151,8 +117,7 @@ def _mix_forward(logits, offs, G, L, mdns, eps):
         heads.append(dict(logit=_at(logits, off * L), log_sigma=_at(ls), mu=_at(mu), eps=_at(e), pred=_at(pred), D=D,
                           f64=int(mu.dtype == torch.float64)))
     arr = (_MixHead * len(heads))(*[_MixHead(**h) for h in heads])
-    _lib.check(_lib.lib().p2r_mdn_mix_forward(len(heads), arr, B, G, L, logits.shape[1],
-                                              _lib.current_stream(logits.device)), "mdn_mix_forward")
+    _lib.launch_on('p2r_mdn_mix_forward', _lib.current_stream(logits.device), len(heads), arr, B, G, L, logits.shape[1])
     return preds
 
 
@@ -171,8 +136,8 @@ def _mix_backward(logits, dlogits, offs, G, L, mdns, eps, dpreds):
                           dmu=_at(dmu), dlogit=_at(dlogits, off * L), dlog_sigma=_at(dls), D=D,
                           f64=int(mu.dtype == torch.float64)))
     arr = (_MixHead * len(heads))(*[_MixHead(**h) for h in heads])
-    _lib.check(_lib.lib().p2r_mdn_mix_backward(len(heads), arr, B, G, L, logits.shape[1], dlogits.shape[1],
-                                               _lib.current_stream(logits.device)), "mdn_mix_backward")
+    _lib.launch_on('p2r_mdn_mix_backward', _lib.current_stream(logits.device), len(heads), arr, B, G, L, logits.shape[1],
+                   dlogits.shape[1])
     return dmus, dlss
 
 
@@ -569,9 +534,7 @@ class _VoteFinish(Function):
         dev = sf.device
         f32 = dict(dtype=torch.float32, device=dev)
         xyz, feat, inv = torch.empty((B, S, 3), **f32), torch.empty((B, 256, S), **f32), torch.empty((B, S), **f32)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().p2r_vote_finish(B, S, 256, _lib.ptr(net), _lib.ptr(sf), _lib.ptr(hip), _lib.ptr(xyz),
-                                                  _lib.ptr(feat), _lib.ptr(inv), _lib.current_stream(dev)), "vote_finish")
+        _lib.launch('p2r_vote_finish', dev, B, S, 256, net, sf, hip, xyz, feat, inv)
         ctx.save_for_backward(feat, inv)
         ctx.set_materialize_grads(False)
         return xyz, feat
@@ -585,10 +548,7 @@ class _VoteFinish(Function):
         d_sf = torch.empty((B, S, 256), dtype=torch.float32, device=dev)
         d_xyz = d_xyz.contiguous() if d_xyz is not None else None
         d_feat = d_feat.contiguous() if d_feat is not None else None
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().p2r_vote_finish_grad(B, S, 256, _lib.ptr(d_xyz), _lib.ptr(d_feat), _lib.ptr(feat),
-                                                       _lib.ptr(inv), _lib.ptr(d_net), _lib.ptr(d_sf),
-                                                       _lib.current_stream(dev)), "vote_finish_grad")
+        _lib.launch('p2r_vote_finish_grad', dev, B, S, 256, d_xyz, d_feat, feat, inv, d_net, d_sf)
         return d_net, d_sf, d_xyz          # hip: vote_xyz = hip + offset
 
 

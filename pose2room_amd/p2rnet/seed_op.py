@@ -1,8 +1,6 @@
 """Seams of the ST-GCN backbone on the streaming kernels of csrc/seed_ops.hip: the frame gather in front of
 `conv_joint` (reference models/p2rnet/modules/stgcn.py:142-149) and the two short-row reductions of the embedding
 (stgcn.py:118-121,129-130).  Each replaces an ATen advanced-indexing / reduction chain by one launch each way."""
-import ctypes
-
 import torch
 from torch.autograd import Function
 
@@ -12,9 +10,7 @@ from .. import _lib
 def _rowsum(x, V, scale):
     """x: contiguous f32 with a trailing axis of length V -> x.sum(-1) * scale"""
     out = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().p2r_rowsum_short(ctypes.c_longlong(x.numel() // V), V, ctypes.c_float(scale), _lib.ptr(x),
-                                               _lib.ptr(out), _lib.current_stream(x.device)), "rowsum_short")
+    _lib.launch("p2r_rowsum_short", x.device, x.numel() // V, V, scale, x, out)
     return out
 
 
@@ -32,9 +28,7 @@ class _SeedRows(Function):
         B, C, T, J = x.shape
         S = inds.shape[1]
         out = torch.empty((B, S, C * J), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().p2r_gather_frames(B, C, T, J, S, _lib.ptr(x), _lib.ptr(inds), _lib.ptr(out),
-                                                    _lib.current_stream(x.device)), "gather_frames")
+        _lib.launch("p2r_gather_frames", x.device, B, C, T, J, S, x, inds, out)
         ctx.save_for_backward(inds)
         ctx.dims = (B, C, T, J, S)
         return out
@@ -45,9 +39,7 @@ class _SeedRows(Function):
         B, C, T, J, S = ctx.dims
         dout = dout.contiguous()
         dx = torch.empty((B, C, T, J), dtype=torch.float32, device=dout.device)
-        with torch.cuda.device(dout.device):
-            _lib.check(_lib.lib().p2r_gather_frames_grad(B, C, T, J, S, _lib.ptr(dout), _lib.ptr(inds), _lib.ptr(dx),
-                                                         _lib.current_stream(dout.device)), "gather_frames_grad")
+        _lib.launch("p2r_gather_frames_grad", dout.device, B, C, T, J, S, dout, inds, dx)
         return dx, None
 
 
@@ -108,7 +100,5 @@ def nearest_prefix(cum, target):
     B, T = cum.shape
     S = target.shape[1]
     out = torch.empty((B, S), dtype=torch.int64, device=cum.device)
-    with torch.cuda.device(cum.device):
-        _lib.check(_lib.lib().p2r_nearest_prefix(B, T, S, _lib.ptr(cum), _lib.ptr(target), _lib.ptr(out),
-                                                 _lib.current_stream(cum.device)), "nearest_prefix")
+    _lib.launch("p2r_nearest_prefix", cum.device, B, T, S, cum, target, out)
     return out

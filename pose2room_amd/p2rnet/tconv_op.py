@@ -82,11 +82,8 @@ def _tconvh(x, scale, shift, st, bias, want_stats=False, bwd=None, x_word=None):
     if want_stats:      # one partial per workgroup = per (sample, chunk of frames)
         part = torch.empty((N * (T // chunk), C, 3 if bwd is None else 2), dtype=torch.float32, device=x.device)
     bz, bfin = (bwd[0], bwd[1].contiguous()) if bwd is not None else (None, None)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().p2r_stgcn_tconvh_forward(
-            N, T, V, _lib.ptr(x), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(st.wh), _lib.ptr(st.winv), _lib.ptr(bias),
-            _lib.ptr(out), _lib.ptr(part), None, _lib.ptr(bz), _lib.ptr(bfin), _lib.ptr(x_word),
-            _lib.current_stream(x.device)), "stgcn_tconvh_forward")
+    _lib.launch("p2r_stgcn_tconvh_forward", x.device, N, T, V, x, scale, shift, st.wh, st.winv, bias, out, part, None, bz,
+                bfin, x_word)
     return (out, part) if want_stats else out
 
 
@@ -96,7 +93,6 @@ def _tconv(x, scale, shift, W3, bias, want_stats=False, bwd=None, Wp=None):
     A-operand order (`_permute_taps`), W3 may then be None."""
     N, C, T, V = x.shape
     out = torch.empty_like(x)
-    lib = _lib.lib()
     part = None
     if Wp is not None or _tconv2_able(W3, V):          # second-generation kernel
         if Wp is None:
@@ -111,22 +107,18 @@ def _tconv(x, scale, shift, W3, bias, want_stats=False, bwd=None, Wp=None):
                 #                 of the third generation write (count, mean, M2) entries, everything else pairs of sums
                 part = torch.empty((min(N * ((T + 15) // 16), 256), C, 3 if gen3 and bwd is None else 2),
                                    dtype=torch.float32, device=x.device)
-            fn = lib.p2r_stgcn_tconv3_forward if gen3 else lib.p2r_stgcn_tconv2_forward
-            _lib.check(fn(N, T, V, Wp.shape[0], _lib.ptr(x), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(Wp),
-                          _lib.ptr(bias), _lib.ptr(out), _lib.ptr(part), None, _lib.ptr(bz), _lib.ptr(bfin), st),
-                       "stgcn_tconv3_forward" if gen3 else "stgcn_tconv2_forward")
+            _lib.launch_on("p2r_stgcn_tconv3_forward" if gen3 else "p2r_stgcn_tconv2_forward", st, N, T, V, Wp.shape[0], x,
+                           scale, shift, Wp, bias, out, part, None, bz, bfin)
         return (out, part) if want_stats else out
     assert bwd is None
     with torch.cuda.device(x.device):
         st = _lib.current_stream(x.device)
         if want_stats:      # one (sum, sum of squares) partial per persistent workgroup: ask how many
             n = ctypes.c_int(0)
-            _lib.check(lib.p2r_stgcn_tconv_forward(N, T, V, W3.shape[0], None, None, None, None, None, None, None,
-                                                   ctypes.byref(n), st), "stgcn_tconv_forward(size)")
+            _lib.check(_lib.lib().p2r_stgcn_tconv_forward(N, T, V, W3.shape[0], None, None, None, None, None, None, None,
+                                                          ctypes.byref(n), st), "stgcn_tconv_forward(size)")
             part = torch.empty((n.value, C, 2), dtype=torch.float32, device=x.device)
-        _lib.check(lib.p2r_stgcn_tconv_forward(N, T, V, W3.shape[0], _lib.ptr(x), _lib.ptr(scale), _lib.ptr(shift),
-                                               _lib.ptr(W3), _lib.ptr(bias), _lib.ptr(out), _lib.ptr(part), None, st),
-                   "stgcn_tconv_forward")
+        _lib.launch_on("p2r_stgcn_tconv_forward", st, N, T, V, W3.shape[0], x, scale, shift, W3, bias, out, part, None)
     return (out, part) if want_stats else out
 
 
@@ -149,11 +141,8 @@ class _BNReLUTConv(Function):
             if (USE_GEN3 and V == 53 and T % 16 == 0 and z.data_ptr() % 16 == 0 and add_c.shape == (N, C, T)
                     and add_c.dtype == torch.float32):
                 out = torch.empty_like(z)
-                with torch.cuda.device(z.device):
-                    _lib.check(_lib.lib().p2r_stgcn_tconv3_forward_add(
-                        N, T, V, _lib.ptr(z), _lib.ptr(fin[2]), _lib.ptr(fin[3]), _lib.ptr(_permute_taps(W3)),
-                        _lib.ptr(bias.contiguous() if bias is not None else None), _lib.ptr(add_c), _lib.ptr(out),
-                        _lib.current_stream(z.device)), "stgcn_tconv3_forward_add")
+                _lib.launch("p2r_stgcn_tconv3_forward_add", z.device, N, T, V, z, fin[2], fin[3], _permute_taps(W3),
+                            bias.contiguous() if bias is not None else None, add_c, out)
             else:
                 out = _tconv(z, fin[2], fin[3], W3, bias.contiguous() if bias is not None else None) + add_c.unsqueeze(-1)
             ctx.save_for_backward(z, fin, W3)
@@ -195,7 +184,6 @@ class _BNReLUTConv(Function):
         N, C, T, V = z.shape
         L = T * V
         dev = z.device
-        lib = _lib.lib()
         st = _lib.current_stream(dev)
         # dh[ci, t] = sum_p W[p][c][ci] du[c, t - (p-1)]  ->  same kernel, taps reversed + transposed
         wp_b = ctx.wp_b
@@ -219,9 +207,7 @@ class _BNReLUTConv(Function):
         with torch.cuda.device(dev):
             if need_sums and part is None:
                 part = torch.empty((N, C, 2), dtype=torch.float32, device=dev)
-                _lib.check(lib.p2r_bn_bwd_reduce(N, C, L, _lib.ptr(dh), None, _lib.ptr(z), _lib.ptr(mean),
-                                                 _lib.ptr(invstd), 2, _lib.ptr(scale), _lib.ptr(shift),
-                                                 _lib.ptr(part), st), "bn_bwd_reduce")
+                _lib.launch_on("p2r_bn_bwd_reduce", st, N, C, L, dh, None, z, mean, invstd, 2, scale, shift, part)
             if ctx.train:
                 tot = bn_op.bwd_finalize(part, N * L)              # (dbeta, dgamma, m1, m2)
                 dbeta, dgamma, m1, m2, m12 = tot[0], tot[1], tot[2], tot[3], tot[2:]
@@ -240,24 +226,17 @@ class _BNReLUTConv(Function):
             if FUSE_DZ and taps == 3 and V == 53 and split:
                 # ... and, in split16 mode, leaves the range word of dz for the graph conv's gradient kernels
                 word = math_mode.new_word(dev)
-                _lib.check(lib.p2r_stgcn_tconv_weight_grad_dz_amax(
-                    N, T, V, taps, _lib.ptr(z), _lib.ptr(fin), _lib.ptr(du), _lib.ptr(dh), _lib.ptr(m12), _lib.ptr(dz),
-                    _N_BLOCKS, _lib.ptr(part), _lib.ptr(bpart), _lib.ptr(word), st), "stgcn_tconv_weight_grad_dz_amax")
+                _lib.launch_on("p2r_stgcn_tconv_weight_grad_dz_amax", st, N, T, V, taps, z, fin, du, dh, m12, dz, _N_BLOCKS,
+                               part, bpart, word)
                 math_mode.announce(dz, word)
             elif FUSE_DZ and taps == 3 and V == 53:
                 # the BatchNorm-backward apply pass rides on the weight-gradient kernel's tile staging (it holds z)
-                _lib.check(lib.p2r_stgcn_tconv_weight_grad_dz(N, T, V, taps, _lib.ptr(z), _lib.ptr(fin), _lib.ptr(du),
-                                                              _lib.ptr(dh), _lib.ptr(m12), _lib.ptr(dz), _N_BLOCKS,
-                                                              _lib.ptr(part), _lib.ptr(bpart), st),
-                           "stgcn_tconv_weight_grad_dz")
+                _lib.launch_on("p2r_stgcn_tconv_weight_grad_dz", st, N, T, V, taps, z, fin, du, dh, m12, dz, _N_BLOCKS, part,
+                               bpart)
             else:
-                _lib.check(lib.p2r_bn_bwd_apply(N, C, L, _lib.ptr(dh), None, _lib.ptr(z), _lib.ptr(mean),
-                                                _lib.ptr(invstd), _lib.ptr(scale), _lib.ptr(m1), _lib.ptr(m2), 2,
-                                                _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(dz), None, st),
-                           "bn_bwd_apply")
-                _lib.check(lib.p2r_stgcn_tconv_weight_grad(N, T, V, taps, _lib.ptr(z), _lib.ptr(scale),
-                                                           _lib.ptr(shift), _lib.ptr(du), _N_BLOCKS, _lib.ptr(part),
-                                                           _lib.ptr(bpart), st), "stgcn_tconv_weight_grad")
+                _lib.launch_on("p2r_bn_bwd_apply", st, N, C, L, dh, None, z, mean, invstd, scale, m1, m2, 2, scale, shift,
+                               dz, None)
+                _lib.launch_on("p2r_stgcn_tconv_weight_grad", st, N, T, V, taps, z, scale, shift, du, _N_BLOCKS, part, bpart)
             dW = _lib.sum_leading(part).view(ctx.wshape)      # the kernel writes its partials in the weight's own (c, ci, tap) order
             if ctx.has_bias:        # row sums of du ride on the weight-gradient pass
                 dbias = _lib.sum_leading(bpart)
@@ -294,15 +273,13 @@ class _Embed3(Function):
         w2, b1 = weight.reshape(64, 3).contiguous(), (bias.contiguous() if bias is not None else None)
         stats = None
         with torch.cuda.device(x.device):
+            st = _lib.current_stream(x.device)
             if want_stats:      # batch statistics of the output from the moments of the three input rows
                 stats = torch.empty((1, 64, 3), dtype=torch.float32, device=x.device)
                 scratch = torch.empty((B * ((L + 1023) // 1024), 10), dtype=torch.float32, device=x.device)
-                _lib.check(_lib.lib().p2r_embed3_forward_stats(B, L, _lib.ptr(x), _lib.ptr(w2), _lib.ptr(b1), _lib.ptr(out),
-                                                               _lib.ptr(scratch), _lib.ptr(stats),
-                                                               _lib.current_stream(x.device)), "embed3_forward_stats")
+                _lib.launch_on("p2r_embed3_forward_stats", st, B, L, x, w2, b1, out, scratch, stats)
             else:
-                _lib.check(_lib.lib().p2r_embed3_forward(B, L, _lib.ptr(x), _lib.ptr(w2), _lib.ptr(b1), _lib.ptr(out),
-                                                         _lib.current_stream(x.device)), "embed3_forward")
+                _lib.launch_on("p2r_embed3_forward", st, B, L, x, w2, b1, out)
         ctx.save_for_backward(x)
         ctx.has_bias = bias is not None
         ctx.wshape = weight.shape
@@ -318,9 +295,7 @@ class _Embed3(Function):
         dout = dout.contiguous()
         B, _, L = x.shape
         part = torch.empty((B * 64, 4), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().p2r_embed3_weight_grad(B, L, _lib.ptr(x), _lib.ptr(dout), _lib.ptr(part),
-                                                         _lib.current_stream(x.device)), "embed3_weight_grad")
+        _lib.launch("p2r_embed3_weight_grad", x.device, B, L, x, dout, part)
         tot = part.view(B, 64, 4).double().sum(0).float()
         return None, tot[:, :3].reshape(ctx.wshape).contiguous(), (tot[:, 3].contiguous() if ctx.has_bias else None), None
 

@@ -16,14 +16,9 @@ Behavioural contract kept from the reference wrappers:
 Unlike the reference, a failed launch raises instead of calling exit(-1)
 (include/cuda_utils.h:30-39).
 """
-import ctypes
-
 import torch
 
 from .. import _lib
-
-_c_int = ctypes.c_int
-_c_float = ctypes.c_float
 
 
 def _check(t, name, dtype):
@@ -43,10 +38,6 @@ def _same_device(a, b, name):
         raise RuntimeError(f"{name} must be on the same GPU as the first argument")
 
 
-def _stream(t):
-    return _lib.current_stream(t.device)
-
-
 _FPS_COOP_MIN_N = 16384      # csrc/fps.hip: largest cloud one workgroup holds in registers
 
 
@@ -61,10 +52,7 @@ def furthest_point_sampling(points, nsamples):
     tmp = None
     if n > 16384:
         tmp = torch.empty((b, n), dtype=torch.float32, device=points.device)
-    with torch.cuda.device(points.device):
-        _lib.check(_lib.lib().p2r_furthest_point_sampling(
-            _c_int(b), _c_int(n), _c_int(nsamples), _lib.ptr(points), _lib.ptr(tmp),
-            _lib.ptr(output), _stream(points)), "furthest_point_sampling")
+    _lib.launch("p2r_furthest_point_sampling", points.device, b, n, nsamples, points, tmp, output)
     if n > _FPS_COOP_MIN_N and b > 0 and nsamples > 0:
         # clouds beyond one workgroup's registers may run on several co-operating workgroups (csrc/fps.hip).  Should
         # a peer workgroup not show up within the kernel's spin bound the remaining picks come back as -1; surface
@@ -84,10 +72,7 @@ def gather_points(points, idx):
     b, c, n = points.shape
     m = idx.size(1)
     output = torch.empty((b, c, m), dtype=torch.float32, device=points.device)
-    with torch.cuda.device(points.device):
-        _lib.check(_lib.lib().p2r_gather_points(
-            _c_int(b), _c_int(c), _c_int(n), _c_int(m), _lib.ptr(points), _lib.ptr(idx),
-            _lib.ptr(output), _stream(points)), "gather_points")
+    _lib.launch("p2r_gather_points", points.device, b, c, n, m, points, idx, output)
     return output
 
 
@@ -98,10 +83,7 @@ def gather_points_grad(grad_out, idx, n):
     _same_device(grad_out, idx, "idx")
     b, c, m = grad_out.shape
     output = torch.empty((b, c, n), dtype=torch.float32, device=grad_out.device)
-    with torch.cuda.device(grad_out.device):
-        _lib.check(_lib.lib().p2r_gather_points_grad(
-            _c_int(b), _c_int(c), _c_int(n), _c_int(m), _lib.ptr(grad_out), _lib.ptr(idx),
-            _lib.ptr(output), _stream(grad_out)), "gather_points_grad")
+    _lib.launch("p2r_gather_points_grad", grad_out.device, b, c, n, m, grad_out, idx, output)
     return output
 
 
@@ -113,10 +95,7 @@ def ball_query(new_xyz, xyz, radius, nsample):
     b, m = new_xyz.size(0), new_xyz.size(1)
     n = xyz.size(1)
     idx = torch.empty((b, m, nsample), dtype=torch.int32, device=new_xyz.device)
-    with torch.cuda.device(new_xyz.device):
-        _lib.check(_lib.lib().p2r_ball_query(
-            _c_int(b), _c_int(n), _c_int(m), _c_float(radius), _c_int(nsample),
-            _lib.ptr(new_xyz), _lib.ptr(xyz), _lib.ptr(idx), _stream(new_xyz)), "ball_query")
+    _lib.launch("p2r_ball_query", new_xyz.device, b, n, m, radius, nsample, new_xyz, xyz, idx)
     return idx
 
 
@@ -128,10 +107,7 @@ def group_points(points, idx):
     b, c, n = points.shape
     npoints, nsample = idx.size(1), idx.size(2)
     output = torch.empty((b, c, npoints, nsample), dtype=torch.float32, device=points.device)
-    with torch.cuda.device(points.device):
-        _lib.check(_lib.lib().p2r_group_points(
-            _c_int(b), _c_int(c), _c_int(n), _c_int(npoints), _c_int(nsample), _lib.ptr(points),
-            _lib.ptr(idx), _lib.ptr(output), _stream(points)), "group_points")
+    _lib.launch("p2r_group_points", points.device, b, c, n, npoints, nsample, points, idx, output)
     return output
 
 
@@ -142,10 +118,7 @@ def group_points_grad(grad_out, idx, n):
     _same_device(grad_out, idx, "idx")
     b, c, npoints, nsample = grad_out.shape
     output = torch.empty((b, c, n), dtype=torch.float32, device=grad_out.device)
-    with torch.cuda.device(grad_out.device):
-        _lib.check(_lib.lib().p2r_group_points_grad(
-            _c_int(b), _c_int(c), _c_int(n), _c_int(npoints), _c_int(nsample), _lib.ptr(grad_out),
-            _lib.ptr(idx), _lib.ptr(output), _stream(grad_out)), "group_points_grad")
+    _lib.launch("p2r_group_points_grad", grad_out.device, b, c, n, npoints, nsample, grad_out, idx, output)
     return output
 
 
@@ -159,10 +132,7 @@ def three_nn(unknowns, knows):
     m = knows.size(1)
     idx = torch.empty((b, n, 3), dtype=torch.int32, device=unknowns.device)
     dist2 = torch.empty((b, n, 3), dtype=torch.float32, device=unknowns.device)
-    with torch.cuda.device(unknowns.device):
-        _lib.check(_lib.lib().p2r_three_nn(
-            _c_int(b), _c_int(n), _c_int(m), _lib.ptr(unknowns), _lib.ptr(knows), _lib.ptr(dist2),
-            _lib.ptr(idx), _stream(unknowns)), "three_nn")
+    _lib.launch("p2r_three_nn", unknowns.device, b, n, m, unknowns, knows, dist2, idx)
     return [dist2, idx]
 
 
@@ -177,10 +147,7 @@ def three_interpolate(points, idx, weight):
     b, c, m = points.shape
     n = idx.size(1)
     output = torch.empty((b, c, n), dtype=torch.float32, device=points.device)
-    with torch.cuda.device(points.device):
-        _lib.check(_lib.lib().p2r_three_interpolate(
-            _c_int(b), _c_int(c), _c_int(m), _c_int(n), _lib.ptr(points), _lib.ptr(idx),
-            _lib.ptr(weight), _lib.ptr(output), _stream(points)), "three_interpolate")
+    _lib.launch("p2r_three_interpolate", points.device, b, c, m, n, points, idx, weight, output)
     return output
 
 
@@ -193,8 +160,5 @@ def three_interpolate_grad(grad_out, idx, weight, m):
     _same_device(grad_out, weight, "weight")
     b, c, n = grad_out.shape
     output = torch.empty((b, c, m), dtype=torch.float32, device=grad_out.device)
-    with torch.cuda.device(grad_out.device):
-        _lib.check(_lib.lib().p2r_three_interpolate_grad(
-            _c_int(b), _c_int(c), _c_int(n), _c_int(m), _lib.ptr(grad_out), _lib.ptr(idx),
-            _lib.ptr(weight), _lib.ptr(output), _stream(grad_out)), "three_interpolate_grad")
+    _lib.launch("p2r_three_interpolate_grad", grad_out.device, b, c, n, m, grad_out, idx, weight, output)
     return output

@@ -4,8 +4,6 @@ ReLU) + max-pool in one HIP launch on fp32 MFMA (csrc/sa_votes.hip), forward and
 `PointnetSAModuleVotes` uses it on GPU tensors for the P2RNet configuration (mlp = [256, 256, 256], bn off, xyz
 features off, max pooling, nsample 16); anything else runs the differentiable op chain.
 """
-import ctypes
-
 import torch
 import torch.nn as nn
 from torch.autograd import Function
@@ -43,11 +41,8 @@ def _forward(xyz, new_xyz, features, radius, nsample, w1, b1, w2, b2, train):
         G = torch.empty((B, 256, M, nsample), dtype=torch.float32, device=dev)
         H = torch.empty((B, 256, M, nsample), dtype=torch.float32, device=dev)
         amax = torch.empty((B, 256, M), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().p2r_sa_votes_forward(
-            B, N, M, nsample, ctypes.c_float(radius), 256, 256, 256, _lib.ptr(xyz), _lib.ptr(new_xyz),
-            _lib.ptr(features), _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(w2), _lib.ptr(b2), _lib.ptr(idx), _lib.ptr(out),
-            _lib.ptr(G), _lib.ptr(H), _lib.ptr(amax), _lib.current_stream(dev)), "sa_votes_forward")
+    _lib.launch("p2r_sa_votes_forward", dev, B, N, M, nsample, radius, 256, 256, 256, xyz, new_xyz, features, w1, b1,
+                w2, b2, idx, out, G, H, amax)
     return out, idx, G, H, amax
 
 
@@ -55,9 +50,7 @@ def _weight_grad(dZ, X):
     """dW (256,256) = sum over samples and positions of dZ . X^T for dZ, X (B,256,M,16)."""
     B, L = dZ.shape[0], dZ.shape[2] * dZ.shape[3]
     part = torch.empty((_SPLIT, 256, 256), dtype=torch.float32, device=dZ.device)
-    with torch.cuda.device(dZ.device):
-        _lib.check(_lib.lib().p2r_gemm_nt_256(B, L, _SPLIT, _lib.ptr(dZ), _lib.ptr(X), _lib.ptr(part),
-                                              _lib.current_stream(dZ.device)), "gemm_nt_256")
+    _lib.launch("p2r_gemm_nt_256", dZ.device, B, L, _SPLIT, dZ, X, part)
     return _lib.sum_leading(part)
 
 
@@ -82,18 +75,14 @@ class _SAVotes(Function):
         S = idx.shape[2]
         dev = out.device
         dZ2, dZ1, dG = (torch.empty((B, C, M, S), dtype=torch.float32, device=dev) for _ in range(3))
-        lib = _lib.lib()
         w2t, w1t = w2c.t().contiguous(), w1c.t().contiguous()     # named: a temporary's block could be handed out again
         with torch.cuda.device(dev):
             st = _lib.current_stream(dev)
-            _lib.check(lib.p2r_sa_votes_backward(B, M, S, C, _lib.ptr(dout), _lib.ptr(out), _lib.ptr(amax), _lib.ptr(H),
-                                                 _lib.ptr(w2t), _lib.ptr(w1t), _lib.ptr(dZ2), _lib.ptr(dZ1),
-                                                 _lib.ptr(dG), st), "sa_votes_backward")
+            _lib.launch_on("p2r_sa_votes_backward", st, B, M, S, C, dout, out, amax, H, w2t, w1t, dZ2, dZ1, dG)
             dfeat = None
             if ctx.needs_input_grad[2]:
                 dfeat = torch.empty((B, C, ctx.n_points), dtype=torch.float32, device=dev)
-                _lib.check(lib.p2r_group_points_grad(B, C, ctx.n_points, M, S, _lib.ptr(dG), _lib.ptr(idx),
-                                                     _lib.ptr(dfeat), st), "group_points_grad")
+                _lib.launch_on("p2r_group_points_grad", st, B, C, ctx.n_points, M, S, dG, idx, dfeat)
         dw1 = _weight_grad(dZ1, G).view(ctx.shapes[0]) if ctx.needs_input_grad[3] else None
         dw2 = _weight_grad(dZ2, H).view(ctx.shapes[1]) if ctx.needs_input_grad[5] else None
         db1 = dZ1.sum(dim=(0, 2, 3)) if ctx.needs_input_grad[4] else None

@@ -245,3 +245,35 @@ def test_sa_votes_fused_backward(ext, oracle, dev, B, N, M, kind):
             scale = max(ref[4][n].abs().max().item(), 1e-6)
             err = (got[4][n] - ref[4][n]).abs().max().item()
             assert err <= 1e-3 * scale, f'{n}: {err:.3e} vs scale {scale:.3e}'
+
+
+def test_launch_helper_matches_raw_ctypes_calls(ext, oracle, dev):
+    """the scalars the launch helper converts by the header's argtypes (a long long, a float) reach the kernels: the
+    helper path against the raw ctypes path with hand-wrapped scalars, bit for bit"""
+    import ctypes
+    from pose2room_amd import _lib
+    # p2r_sum_leading: P = 3 rows of M = 8 floats (the smallest M % 4 == 0 with a second 16-byte row), M a plain int
+    part = cases.seeded_randn((3, 8), 11).to(dev)
+    raw, got = (torch.full((8,), float('nan'), device=dev) for _ in range(2))
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().p2r_sum_leading(3, ctypes.c_longlong(8), _lib.ptr(part), _lib.ptr(raw), 0,
+                                              _lib.current_stream(dev)), "sum_leading")
+    _lib.launch('p2r_sum_leading', dev, 3, 8, part, got, 0)
+    assert torch.equal(got, raw) and torch.equal(_lib.sum_leading(part), raw)
+    # three fp32 additions per element: each rounds by at most 2^-24 of a partial sum <= sum |x|
+    bound = 3 * 2.0 ** -24 * part.double().abs().sum(0)
+    assert torch.all((raw.double() - part.double().sum(0)).abs() <= bound)
+    # p2r_ball_query: eight points 0.25 apart on a line, radius a Python float that separates the neighbours
+    xyz = torch.zeros(1, 8, 3)
+    xyz[0, :, 0] = 0.25 * torch.arange(8)
+    new_xyz = xyz[:, [0, 4]].contiguous()
+    want = oracle.OracleExt.ball_query(new_xyz, xyz, 0.3, 4)
+    assert want.tolist() == [[[0, 1, 0, 0], [3, 4, 5, 3]]]
+    xd, nd = xyz.to(dev), new_xyz.to(dev)
+    raw, got = (torch.full((1, 2, 4), -7, dtype=torch.int32, device=dev) for _ in range(2))
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().p2r_ball_query(1, 8, 2, ctypes.c_float(0.3), 4, _lib.ptr(nd), _lib.ptr(xd), _lib.ptr(raw),
+                                             _lib.current_stream(dev)), "ball_query")
+    _lib.launch('p2r_ball_query', dev, 1, 8, 2, 0.3, 4, nd, xd, got)
+    assert torch.equal(got, raw) and torch.equal(got.cpu(), want)
+    assert torch.equal(ext.ball_query(nd, xd, 0.3, 4), raw)
