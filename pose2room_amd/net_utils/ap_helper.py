@@ -246,6 +246,27 @@ def assembly_gt_map_cls(parsed_gts, mesh_outputs=None, voxel_size=0.047):
             for i in range(sem_cls_label.shape[0])]
 
 
+def metrics_from_curves(rec, ap, class2type_map=None):
+    """{class: rec}, {class: ap} of `eval_det_multiprocessing_wo_mesh` -> the metric dict of
+    `APCalculator.compute_metrics` (ap_helper.py:60-84): '<cls> Average Precision' per class, 'mAP', '<cls> Recall'
+    per class, 'AR'.  Shared by `APCalculator` and `ap_device.DeviceAPCalculator`."""
+    name = (lambda k: class2type_map[k]) if class2type_map else str
+    ret = {}
+    for key in sorted(ap.keys()):
+        ret['%s Average Precision' % name(key)] = ap[key]
+    ret['mAP'] = np.mean([v for v in ap.values() if not np.isnan(v)])
+    recalls = []
+    for key in sorted(ap.keys()):
+        try:
+            last = rec[key][-1]
+        except (TypeError, IndexError):      # class without predictions (rec == 0) or without detections
+            last = 0
+        ret['%s Recall' % name(key)] = last
+        recalls.append(last)
+    ret['AR'] = np.mean([v for v in recalls if not np.isnan(v)])
+    return ret
+
+
 class APCalculator(object):
     """Accumulates per-scan predictions / ground truths and computes AP, mAP, recall and AR
     (net_utils/ap_helper.py:24-128, mesh-free branch; the class P2RNet's test loop instantiates with
@@ -274,21 +295,7 @@ class APCalculator(object):
         from .eval_det import eval_det_multiprocessing_wo_mesh
         rec, _, ap = eval_det_multiprocessing_wo_mesh(self.pred_map_cls, self.gt_map_cls, ovthresh=self.ap_iou_thresh,
                                                       device=self.device)
-        name = (lambda k: self.class2type_map[k]) if self.class2type_map else str
-        ret = {}
-        for key in sorted(ap.keys()):
-            ret['%s Average Precision' % name(key)] = ap[key]
-        ret['mAP'] = np.mean([v for v in ap.values() if not np.isnan(v)])
-        recalls = []
-        for key in sorted(ap.keys()):
-            try:
-                last = rec[key][-1]
-            except (TypeError, IndexError):      # class without predictions (rec == 0) or without detections
-                last = 0
-            ret['%s Recall' % name(key)] = last
-            recalls.append(last)
-        ret['AR'] = np.mean([v for v in recalls if not np.isnan(v)])
-        return ret
+        return metrics_from_curves(rec, ap, self.class2type_map)
 
     def reset(self):
         self.gt_map_cls = {}

@@ -36,6 +36,16 @@ def voc_ap(rec, prec, use_07_metric=False):
     return np.sum((mrec[step + 1] - mrec[step]) * mpre[step + 1])
 
 
+def curve_from_flags(tp, fp, npos, use_07_metric=False):
+    """Per-detection true / false positive flags in descending score order and the number of ground truths ->
+    (rec, prec, ap) (eval_det.py:333-343).  Shared by the host sweep below and `ap_device.DeviceAPCalculator`."""
+    fp, tp = np.cumsum(fp), np.cumsum(tp)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        rec = tp / float(npos)
+    prec = tp / np.maximum(tp + fp, np.finfo(np.float64).eps)
+    return rec, prec, voc_ap(rec, prec, use_07_metric)
+
+
 def get_iou_obb(bb1, bb2):
     """eval_det.py:86-88."""
     return float(box3d_iou_pairs(np.asarray(bb1, dtype=np.float64)[None], np.asarray(bb2, dtype=np.float64)[None])[0][0])
@@ -117,11 +127,7 @@ def eval_det_cls_wo_mesh(pred, gt, ovthresh=0.25, use_07_metric=False, get_iou_f
         else:
             fp[d] = 1.
 
-    fp, tp = np.cumsum(fp), np.cumsum(tp)
-    with np.errstate(divide='ignore', invalid='ignore'):
-        rec = tp / float(npos)
-    prec = tp / np.maximum(tp + fp, np.finfo(np.float64).eps)
-    return rec, prec, voc_ap(rec, prec, use_07_metric)
+    return curve_from_flags(tp, fp, npos, use_07_metric)
 
 
 def eval_det_multiprocessing_wo_mesh(pred_all, gt_all, ovthresh=0.25, use_07_metric=False, get_iou_func=None,

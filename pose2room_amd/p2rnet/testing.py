@@ -78,36 +78,56 @@ class Tester(Trainer):
         return {k: v.item() for k, v in loss_reduced.items()}, est_data
 
 
-def test_func(cfg, tester, batches, ap_device='cpu'):
-    """batches: any iterable of data dicts (the reference passes `test_loader.dataloader`)."""
+def _check_ap_impl(ap_impl):
+    if ap_impl not in ('host', 'device'):
+        raise ValueError("ap_impl must be 'host' or 'device', got %r" % (ap_impl,))
+
+
+def test_func(cfg, tester, batches, ap_device='cpu', ap_impl='host'):
+    """batches: any iterable of data dicts (the reference passes `test_loader.dataloader`).
+    ap_impl 'host': one `APCalculator` per IoU threshold, fed with the per-scan lists (the reference's loop).
+    ap_impl 'device': ONE `ap_device.DeviceAPCalculator` for all thresholds, fed with the end points and the batch on
+    the device; `calculators` is then that one calculator in a list."""
+    _check_ap_impl(ap_impl)
     mode = cfg.config['mode']
     recorder = LossRecorder(cfg.config[mode]['batch_size'])
-    calculators = [APCalculator(thr, getattr(cfg.dataset_config, 'class2type', None), False, device=ap_device)
-                   for thr in cfg.config[mode]['ap_iou_thresholds']]
+    class2type = getattr(cfg.dataset_config, 'class2type', None)
+    if ap_impl == 'device':
+        from ..net_utils.ap_device import DeviceAPCalculator
+        calculators = [DeviceAPCalculator(list(cfg.config[mode]['ap_iou_thresholds']), class2type,
+                                          num_class=cfg.dataset_config.num_class,
+                                          per_class_proposal=cfg.eval_config['per_class_proposal'],
+                                          conf_thresh=cfg.eval_config['conf_thresh'])]
+    else:
+        calculators = [APCalculator(thr, class2type, False, device=ap_device) for thr in cfg.config[mode]['ap_iou_thresholds']]
     for data in batches:
         loss, est_data = tester.test_step(data)
-        eval_dict = est_data[1]
-        for calc in calculators:
-            calc.step(eval_dict['batch_pred_map_cls'], eval_dict['batch_gt_map_cls'])
+        if ap_impl == 'device':
+            calculators[0].step_end_points(est_data[0], data, cfg.eval_config)     # test_step moved `data` to the device
+        else:
+            eval_dict = est_data[1]
+            for calc in calculators:
+                calc.step(eval_dict['batch_pred_map_cls'], eval_dict['batch_gt_map_cls'])
         recorder.update_loss(loss)
     recorder.synchronize_between_processes(tester.device)
     return recorder.loss_recorder, calculators
 
 
-def test(cfg, tester, batches, ap_device='cpu'):
-    """test_epoch.py:52-76 -> {'loss': {key: avg}, 'metrics': [{...} per IoU threshold]}; also logged."""
+def test(cfg, tester, batches, ap_device='cpu', ap_impl='host'):
+    """test_epoch.py:52-76 -> {'loss': {key: avg}, 'metrics': [{...} per IoU threshold]}; also logged.
+    ap_impl: 'host' (default) or 'device', see `test_func`; the result has the same shape either way."""
     mode = cfg.config['mode']
     tester.net.train(mode == 'train')
     start = time()
     with torch.no_grad():
-        meters, calculators = test_func(cfg, tester, batches, ap_device)
+        meters, calculators = test_func(cfg, tester, batches, ap_device, ap_impl)
     cfg.log_string('Test time elapsed: (%f).' % (time() - start))
     out = {'loss': {k: m.avg for k, m in meters.items()}, 'metrics': []}
     for key, avg in out['loss'].items():
         cfg.log_string('Test loss (%s): %f' % (key, avg))
-    for thr, calc in zip(cfg.config[mode]['ap_iou_thresholds'], calculators):
+    all_metrics = calculators[0].compute_metrics() if ap_impl == 'device' else [c.compute_metrics() for c in calculators]
+    for thr, metrics in zip(cfg.config[mode]['ap_iou_thresholds'], all_metrics):
         cfg.log_string(('-' * 10 + 'iou_thresh: %f' + '-' * 10) % thr)
-        metrics = calc.compute_metrics()
         for key in metrics:
             cfg.log_string('eval %s: %f' % (key, metrics[key]))
         out['metrics'].append(metrics)
