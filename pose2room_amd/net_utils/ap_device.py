@@ -10,10 +10,10 @@ the device tensors `parse_predictions(..., return_device=True)` returns:
     sweep of eval_det.eval_det_cls_wo_mesh in its parallel form (a detection is a true positive iff its best IoU
     exceeds the threshold and no earlier-ranked detection of the same (scan, class) with the same best ground truth
     does);
-  * `step_tensors` appends scores, flags and ground-truth counts to device-side state without a device->host copy or
-    a synchronisation; `compute_metrics` sorts per class on the device, crosses to the host once with one flag byte
-    per (detection slot, threshold), and finishes with the host expressions `APCalculator` uses
-    (eval_det.curve_from_flags, ap_helper.metrics_from_curves).
+  * `step_tensors` (`match_tensors`, then `append`) adds scores, flags and ground-truth counts to device-side state
+    without a device->host copy or a synchronisation; `compute_metrics` sorts per class on the device, crosses to
+    the host once with one flag byte per (detection slot, threshold), and finishes with the host expressions
+    `APCalculator` uses (eval_det.curve_from_flags, ap_helper.metrics_from_curves).
 
 Equal scores: within one (scan, class) the lower proposal index goes first; across scans the earlier scan.  The
 reference's `np.argsort(-score)` is not stable and defines no order there.  No CPU fallback.
@@ -128,6 +128,40 @@ def curves_from_sorted_flags(flags, npos):
     return rec, prec, ap
 
 
+def match_tensors(pred_corners, pred_mask, obj_prob, sem_cls_scores, pred_sem_cls, gt_corners, gt_cls, gt_mask, thr,
+                  num_class=None, per_class_proposal=True, conf_thresh=0.05):
+    """One step's tensors -> (score (N,K,C) f32, tp (T,N,K,C) u8, npos (N,C) i32), one `obb_iou` and one `ap_match`
+    launch for all N scans: what `DeviceAPCalculator.step_tensors` appends.  The scans are independent, so a slice
+    along N is the result of that slice of the inputs (mm_device.py feeds H calculators from one call).
+    pred_corners (N,K,8,3) f64, pred_mask (N,K), obj_prob (N,K), sem_cls_scores (N,K,C) or None, pred_sem_cls (N,K),
+    gt_corners (N,G,8,3) f64, gt_cls (N,G), gt_mask (N,G), thr (T,) f64: device tensors.  Nothing leaves the device."""
+    _need_cuda("DeviceAPCalculator.step_tensors", pred_corners=pred_corners, pred_mask=pred_mask, obj_prob=obj_prob,
+               sem_cls_scores=sem_cls_scores, pred_sem_cls=pred_sem_cls, gt_corners=gt_corners, gt_cls=gt_cls,
+               gt_mask=gt_mask)
+    dev = pred_corners.device
+    C = num_class if num_class is not None else (None if sem_cls_scores is None else sem_cls_scores.shape[-1])
+    if C is None:
+        raise ValueError("DeviceAPCalculator: num_class is unknown (pass num_class, class2type_map or sem_cls_scores)")
+    obj = obj_prob.to(torch.float32)
+    keep = (pred_mask == 1) & (obj > conf_thresh)                                      # (N,K)
+    if per_class_proposal:
+        if sem_cls_scores is None or sem_cls_scores.shape[-1] != C:
+            raise ValueError(f"DeviceAPCalculator: per-class proposals need sem_cls_scores (B,K,{C})")
+        x = sem_cls_scores.to(torch.float32)
+        e = torch.exp(x - x.max(dim=-1, keepdim=True).values)                          # ap_helper.softmax
+        score = (e / e.sum(dim=-1, keepdim=True)) * obj.unsqueeze(-1)
+        valid = keep.unsqueeze(-1).expand(-1, -1, C)
+    else:
+        own = pred_sem_cls.unsqueeze(-1) == torch.arange(C, device=dev)                # (N,K,C)
+        score = obj.unsqueeze(-1) * own.to(torch.float32)
+        valid = keep.unsqueeze(-1) & own
+    iou3d, _ = obb_iou(pred_corners, gt_corners, want_2d=False)
+    score = score.contiguous()
+    tp, npos = ap_match(iou3d, score, valid.to(torch.uint8).contiguous(), gt_cls.to(torch.int64),
+                        (gt_mask == 1).to(torch.uint8), thr)
+    return score, tp, npos
+
+
 class DeviceAPCalculator(object):
     """AP, mAP, recall and AR of `APCalculator` for one or several IoU thresholds, accumulated on the device.
     ap_iou_thresh: a float (compute_metrics -> one dict) or a sequence of floats (-> a list of dicts, one per
@@ -159,34 +193,20 @@ class DeviceAPCalculator(object):
         """pred_corners (B,K,8,3) f64, pred_mask (B,K), obj_prob (B,K), sem_cls_scores (B,K,C) or None, pred_sem_cls
         (B,K), gt_corners (B,G,8,3) f64, gt_cls (B,G), gt_mask (B,G): device tensors.  Detections are formed as
         assembly_pred_map_cls forms them; ground truths are the slots with gt_mask == 1.  Nothing leaves the device."""
-        _need_cuda("DeviceAPCalculator.step_tensors", pred_corners=pred_corners, pred_mask=pred_mask, obj_prob=obj_prob,
-                   sem_cls_scores=sem_cls_scores, pred_sem_cls=pred_sem_cls, gt_corners=gt_corners, gt_cls=gt_cls,
-                   gt_mask=gt_mask)
-        dev = pred_corners.device
-        C = self.num_class if self.num_class is not None else (None if sem_cls_scores is None else sem_cls_scores.shape[-1])
-        if C is None:
-            raise ValueError("DeviceAPCalculator: num_class is unknown (pass num_class, class2type_map or sem_cls_scores)")
-        obj = obj_prob.to(torch.float32)
-        keep = (pred_mask == 1) & (obj > self.conf_thresh)                                 # (B,K)
-        if self.per_class_proposal:
-            if sem_cls_scores is None or sem_cls_scores.shape[-1] != C:
-                raise ValueError(f"DeviceAPCalculator: per-class proposals need sem_cls_scores (B,K,{C})")
-            x = sem_cls_scores.to(torch.float32)
-            e = torch.exp(x - x.max(dim=-1, keepdim=True).values)                          # ap_helper.softmax
-            score = (e / e.sum(dim=-1, keepdim=True)) * obj.unsqueeze(-1)
-            valid = keep.unsqueeze(-1).expand(-1, -1, C)
-        else:
-            own = pred_sem_cls.unsqueeze(-1) == torch.arange(C, device=dev)                # (B,K,C)
-            score = obj.unsqueeze(-1) * own.to(torch.float32)
-            valid = keep.unsqueeze(-1) & own
-        iou3d, _ = obb_iou(pred_corners, gt_corners, want_2d=False)
-        tp, npos = ap_match(iou3d, score.contiguous(), valid.to(torch.uint8).contiguous(), gt_cls.to(torch.int64),
-                            (gt_mask == 1).to(torch.uint8), self._thresholds(dev))
+        _need_cuda("DeviceAPCalculator.step_tensors", pred_corners=pred_corners)       # its device keys the thresholds
+        self.append(*match_tensors(pred_corners, pred_mask, obj_prob, sem_cls_scores, pred_sem_cls, gt_corners, gt_cls,
+                                   gt_mask, self._thresholds(pred_corners.device), self.num_class,
+                                   self.per_class_proposal, self.conf_thresh))
+
+    def append(self, score, tp, npos):
+        """one step's (score (N,K,C), tp (T,N,K,C), npos (N,C)) of `match_tensors`, or a slice of it along N, joins the
+        state: N more scans"""
+        C = score.shape[-1]
         self._score.append(score.reshape(-1, C))
         self._tp.append(tp.reshape(tp.shape[0], -1, C))
         total = npos.sum(dim=0, dtype=torch.int64)
         self._npos = total if self._npos is None else self._npos + total
-        self.scan_cnt += pred_corners.shape[0]
+        self.scan_cnt += score.shape[0]
 
     def step_end_points(self, est_data, data, eval_config):
         """est_data: end points of `P2RNet.generate` (or its result tuple); data: the batch, on the device."""

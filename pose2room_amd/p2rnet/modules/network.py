@@ -121,7 +121,7 @@ class P2RNet(BaseNetwork):
         return end_points, eval_dict, parsed_predictions
 
     def generate_hypotheses(self, data, num_hypotheses, n_samples=None, seed=None, eval=True, central_tendency=None,
-                            return_draws=False):
+                            return_draws=False, return_device=False):
         """Multi-modal generation (the reference's `multi_mode`, proposal_net.py:56-59 / mdn.py:116-125): H hypotheses
         of the detection for one batch, each one `generate` whose mixture heads return the mean (or the median) of n_h
         Bernoulli-gated draws.  The trunk runs once; the draws of all heads and hypotheses are one kernel launch
@@ -133,10 +133,17 @@ class P2RNet(BaseNetwork):
           return_draws: each hypothesis' end_points gain 'draws' = {'center', 'size', 'heading'}, the heads' individual
           draws (B, K, n_h, D) (the centre's before the vote position is added).
         -> list of H (end_points, eval_dict, parsed_predictions) triples shaped like `generate`'s result; the
-        deterministic end points (votes, aggregation, 'pi', objectness, class scores) are shared by all of them."""
+        deterministic end points (votes, aggregation, 'pi', objectness, class scores) are shared by all of them.
+          return_device: no host lists (`eval` and `return_draws` do not apply); -> ONE dict of device tensors, what
+          `parse_predictions(..., return_device=True)` gives for the H * B batch with the hypotheses as the leading
+          axis: 'end_points' (the shared ones), 'center', 'size', 'heading' (H,B,K,.), 'pred_mask' (H,B,K),
+          'pred_corners_3d' (H,B,K,8,3) f64, 'obj_prob' (H,B,K), 'pred_sem_cls' (H,B,K), 'sem_cls_scores' (H,B,K,C);
+          net_utils/mm_device.py evaluates it without leaving the device."""
         from ...net_utils.ap_helper import (parse_predictions, parse_groundtruths,
                                             assembly_pred_map_cls, assembly_gt_map_cls)
         from .. import mdn_sample_op
+        if return_device and return_draws:
+            raise ValueError("generate_hypotheses: return_draws needs the host form (return_device=False)")
         seed, ns = mdn_sample_op.resolve_draws(num_hypotheses, n_samples, seed)
         H = len(ns)
         xyz, features, end_points = self._votes(data)
@@ -145,6 +152,11 @@ class P2RNet(BaseNetwork):
         B = end_points['aggregated_vote_xyz'].shape[0]
         joints = data['input_joints']
         gt_stacked = {'input_joints': joints.unsqueeze(0).expand(H, *joints.shape).reshape(H * B, *joints.shape[1:])}
+        if return_device:
+            eval_all, parsed_all = parse_predictions(stacked, gt_stacked, self.cfg.eval_config, return_device=True)
+            out = {'end_points': end_points, 'pred_mask': eval_all['pred_mask'], **parsed_all}
+            out.update({k: stacked[k] for k in ('center', 'size', 'heading')})
+            return {k: v if k == 'end_points' else v.reshape(H, B, *v.shape[1:]) for k, v in out.items()}
         eval_all, parsed_all = parse_predictions(stacked, gt_stacked, self.cfg.eval_config)
         gt_map = assembly_gt_map_cls(parse_groundtruths(data, self.cfg.eval_config)) if eval else None
         out = []

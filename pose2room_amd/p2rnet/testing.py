@@ -135,22 +135,31 @@ def test(cfg, tester, batches, ap_device='cpu', ap_impl='host'):
 
 
 def test_multi_modal(cfg, net, batches, num_hypotheses, n_samples=None, seed=None, ap_device='cpu',
-                     dump_threshold=0.5, central_tendency=None):
+                     dump_threshold=0.5, central_tendency=None, impl='host'):
     """Multi-modal evaluation: what `num_hypotheses` reference test runs in multi mode plus
     utils/eval/multi_modal_eval.py produce, from one trunk pass per batch (`P2RNet.generate_hypotheses`).
     Hypothesis h plays run h: its sample counts n_h are fixed for all batches (drawn once from `seed` when None, as
     the reference draws one count per run), one `APCalculator` per IoU threshold collects its detections, and its
     confident boxes (dump_threshold: the reference's generation.dump_threshold) are its dump records.
     net: P2RNet (or a wrapper exposing it as `.module`).  central_tendency: None (the heads' own), 'mean' or 'median'.
+    impl 'host': the reference's evaluation, H x T `APCalculator`s (on `ap_device`) and the NumPy records and TMD.
+    impl 'device': `generate_hypotheses(return_device=True)` into ONE `mm_device.DeviceMultiModalEvaluator`, fed with
+    the batch on the device (`ap_device` does not apply); the result has the same keys and the same log lines.
     -> {'best_map': (T,) max over hypotheses of each threshold's mAP, 'tmd': mean TMD over every (sample, proposal),
         'metrics': [h][t] metric dicts, 'n_samples': [n_h], 'seed': the 64-bit seed,
         'central_tendency': as passed}."""
     from ..net_utils import multi_modal_eval as mm
     from .mdn_sample_op import resolve_draws
+    if impl not in ('host', 'device'):
+        raise ValueError("impl must be 'host' or 'device', got %r" % (impl,))
     model = getattr(net, 'module', net)
     seed, ns = resolve_draws(num_hypotheses, n_samples, seed)
     H = len(ns)
     thresholds = cfg.config[cfg.config['mode']]['ap_iou_thresholds']
+    if impl == 'device':
+        metrics, best, t = _multi_modal_device(cfg, model, batches, H, ns, seed, thresholds, dump_threshold,
+                                               central_tendency)
+        return _multi_modal_result(cfg, H, thresholds, metrics, best, t, ns, seed, central_tendency)
     calcs = [[APCalculator(thr, getattr(cfg.dataset_config, 'class2type', None), False, device=ap_device)
               for thr in thresholds] for _ in range(H)]
     records = [[] for _ in range(H)]
@@ -165,9 +174,37 @@ def test_multi_modal(cfg, net, batches, num_hypotheses, n_samples=None, seed=Non
                 records[h] += mm.confident_boxes(ep, eval_dict, parsed, dump_threshold)
     metrics = [[c.compute_metrics() for c in row] for row in calcs]
     best = mm.best_of_n_map([[m['mAP'] for m in row] for row in metrics])
+    return _multi_modal_result(cfg, H, thresholds, metrics, best, mm.tmd(records), ns, seed, central_tendency)
+
+
+def _multi_modal_result(cfg, H, thresholds, metrics, best, t, ns, seed, central_tendency):
     for thr, v in zip(thresholds, best):
         cfg.log_string('multi-modal (%d hypotheses) iou_thresh %f: best mAP %f' % (H, thr, v))
-    t = mm.tmd(records)
     cfg.log_string('multi-modal TMD: %f' % t)
     return {'best_map': best, 'tmd': t, 'metrics': metrics, 'n_samples': ns, 'seed': seed,
             'central_tendency': central_tendency}
+
+
+def _multi_modal_device(cfg, model, batches, H, ns, seed, thresholds, dump_threshold, central_tendency):
+    """`test_multi_modal(impl='device')`: -> (metrics [h][t], best_map (T,), tmd); the batches must be on the device"""
+    from ..net_utils.ap_helper import boxes_to_corners
+    from ..net_utils.mm_device import DeviceMultiModalEvaluator
+    ev = DeviceMultiModalEvaluator(H, list(thresholds), getattr(cfg.dataset_config, 'class2type', None),
+                                   num_class=cfg.dataset_config.num_class,
+                                   per_class_proposal=cfg.eval_config['per_class_proposal'],
+                                   conf_thresh=cfg.eval_config['conf_thresh'], dump_threshold=dump_threshold)
+    model.train(False)
+    with torch.no_grad():
+        for i, data in enumerate(batches):
+            batch_seed = (seed + i * 0x9E3779B97F4A7C15) & 0xffffffffffffffff     # one stream key per batch
+            hyp = model.generate_hypotheses(data, H, ns, batch_seed, central_tendency=central_tendency,
+                                            return_device=True)
+            mask = data['box_label_mask'].detach()                                # as DeviceAPCalculator.step_end_points
+            gt_heading = torch.atan2(data['heading'][..., 0], data['heading'][..., 1]).detach()
+            corners = boxes_to_corners(torch.exp(data['size']).detach(), gt_heading.to(torch.float64),
+                                       data['center_label'][:, :, 0:3].detach())
+            corners = corners * (mask != 0).to(torch.float64)[:, :, None, None]
+            ev.step_tensors(hyp['pred_corners_3d'], hyp['pred_mask'], hyp['obj_prob'], hyp['sem_cls_scores'],
+                            hyp['pred_sem_cls'], corners, data['sem_cls_label'].detach(), mask)
+    res = ev.compute()
+    return res['metrics'], res['best_map'], res['tmd']
