@@ -1,5 +1,6 @@
 // stgcn_tile.h -- the tile skeleton shared by the 53-joint ST-GCN kernels of the second and third generation
-// (stgcn_gcn2 / gcn3 / gcn3_grad / gcn3h_grad / gcn3_dw / gcn3h_body / tconv2 / tconv3), gfx950.
+// (stgcn_gcn2 / gcn3 / gcn3_dw / tconv2 / tconv3; gcn3_grad / gcn3h_grad, whose common body is stgcn_gcn3_dcoef_body.h;
+// gcn3h_fwd / gcn3h_dx, whose common body is stgcn_gcn3h_body.h), gfx950.
 //
 // The skeleton: a tile of 16 frames x 53 joints, LDS rows of 16 * 53 = 848 floats (848 == 16 mod 32: the two channel
 // rows of a 32-lane read group use disjoint banks); the 64 input channels in four phases of 16 rows through two slice

@@ -116,3 +116,23 @@ def test_shape_restricted_entry_points_refuse_other_shapes():
     assert l.p2r_stgcn_tconv_weight_grad_dz(2, 16, 53, 3, n, n, n, n, n, n, 256, n, n, n) == EINVAL
     assert l.p2r_stgcn_tconv_weight_grad(2, 16, 65, 3, n, n, n, n, 256, n, n, n) == EINVAL
     assert l.p2r_stgcn_tconv_weight_grad(2, 16, 53, 2, n, n, n, n, 256, n, n, n) == EINVAL
+    # adjacency gradient, exact and split16: 53 joints, 11 planes, whole 16-frame tiles, a table, a workgroup, aligned
+    # operands.  Small integers stand for addresses (nothing dereferences them); every case differs in ONE argument from
+    # a call that would launch, and that call itself is never made.
+    ok = dict(N=2, T=16, V=53, K=11, ltot=24, x=64, dz=64, W=64, winv=64, n_blocks=256)
+
+    def exact(**kw):
+        a = dict(ok, **kw)
+        return l.p2r_stgcn_gcn3_coef_grad(a['N'], a['T'], a['V'], a['K'], a['ltot'], a['x'], a['dz'], a['W'],
+                                          a['n_blocks'], 64, n)
+
+    def split(**kw):
+        a = dict(ok, **kw)
+        return l.p2r_stgcn_gcn3h_coef_grad(a['N'], a['T'], a['V'], a['K'], a['ltot'], a['x'], a['dz'], a['W'], a['winv'],
+                                           a['n_blocks'], 64, n, n)
+
+    common = [dict(V=52), dict(K=10), dict(T=40), dict(ltot=0), dict(n_blocks=0), dict(dz=4)]
+    for case in common + [dict(T=(1 << 20) + 16)]:
+        assert exact(**case) == EINVAL, case
+    for case in common + [dict(T=(1 << 19) + 16), dict(x=4), dict(W=n), dict(winv=n), dict(W=8)]:
+        assert split(**case) == EINVAL, case
