@@ -648,14 +648,22 @@ def test_nms3d_batched(oracle, dev, B, K):
 
 
 # ---- detection loss, batch assembly ---------------------------------------------------------------------------------
-@pytest.mark.parametrize("B,S,K,T,case", [(2, 512, 128, 64, 'near'), (2, 64, 128, 32, 'none'), (2, 300, 128, 40, 'ties')])
+@pytest.mark.parametrize("B,S,K,T,case", [(2, 512, 128, 64, 'near'), (2, 64, 128, 32, 'none'), (2, 300, 128, 40, 'ties'),
+                                          (2, 300, 257, 40, 'k257'), (3, 255, 361, 8, 'lds')])
 def test_fused_detection_loss(dev, B, S, K, T, case):
-    """csrc/det_loss.hip against the composed loss: entries 2e-5 / 1e-6, gradients 2e-5 of scale (test_loss_gpu)"""
+    """csrc/det_loss.hip against the composed loss: entries 2e-5 / 1e-6, gradients 2e-5 of scale (test_loss_gpu); 'k257'
+    and 'lds' are the entries of det_loss_cases.SWEEP with a second trip of the proposal loop, 32 ground-truth slots and
+    the dynamic LDS at its limit -- the largest index every output is written at"""
     from pose2room_amd.p2rnet import P2RConfig, default_config
     from pose2room_amd.p2rnet.loss import BoxNetDetectionLoss
+    from tests import det_loss_cases
     cfg = P2RConfig(default_config('train', data={'num_frames': T}), device=dev)
     loss_fn = BoxNetDetectionLoss(1, dev, cfg)
-    est, gt = cases.det_loss_scene(B, S, K, T, seed=B * 1000 + K + T, case=case)
+    if case in ('k257', 'lds'):
+        assert det_loss_cases.BY_ID[case].dims[:4] == (B, S, K, T)
+        est, gt = det_loss_cases.sweep_scene(case)
+    else:
+        est, gt = cases.det_loss_scene(B, S, K, T, seed=B * 1000 + K + T, case=case)
     diff = ['vote_xyz', 'center', 'size', 'heading', 'objectness_scores', 'sem_cls_scores']
     ins = {'e_' + k: Input(v, k in diff) for k, v in est.items()}
     ins.update({'g_' + k: v for k, v in gt.items()})

@@ -126,8 +126,15 @@ def test_ext_argument_checks(ext, dev):
 NND_SHAPES = [(1, 5, 6, 3), (64, 3, 53, 3), (4, 128, 10, 3), (1, 128, 1, 3), (3, 17, 200, 3), (2, 9, 4, 5)]
 
 
-@pytest.mark.parametrize("B,N,M,C", NND_SHAPES)
-@pytest.mark.parametrize("kw", [{}, {"l1smooth": True}, {"l1": True}, {"l1smooth": True, "delta": 0.3}])
+NND_KW = [{}, {"l1smooth": True}, {"l1": True}, {"l1smooth": True, "delta": 0.3}]
+# both kernels cap their grid at 8192 workgroups of 256 and stride beyond 2 097 152 work items: (65537, 16, 16) has
+# 2 097 184 of them in the forward (and three times that in the gradient), (21846, 16, 16) crosses in the gradient only
+NND_CASES = [(kw, i, shape) for i, kw in enumerate(NND_KW) for shape in NND_SHAPES] + \
+    [({}, 0, (65537, 16, 16, 3)), ({"l1smooth": True}, 1, (21846, 16, 16, 3))]
+
+
+@pytest.mark.parametrize("kw,B,N,M,C", [(kw,) + shape for kw, _, shape in NND_CASES],
+                         ids=["kw%d-%d-%d-%d-%d" % ((i,) + shape) for _, i, shape in NND_CASES])
 def test_nn_distance_bit_exact(oracle, dev, B, N, M, C, kw):
     from pose2room_amd.net_utils.nn_distance import nn_distance
     g = torch.Generator().manual_seed(B * 1000 + N * 10 + M)
