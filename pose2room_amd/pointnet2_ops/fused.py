@@ -95,7 +95,7 @@ def sa_votes(xyz, new_xyz, features, radius, nsample, mlp_module, return_idx=Fal
     features and the four MLP tensors (the sampled centres and the ball membership carry no gradient, as in the
     reference's ball_query / group_points)."""
     c1, _, c2, _ = mlp_module
-    if torch.is_grad_enabled() and (features.requires_grad or c1.weight.requires_grad or c2.weight.requires_grad):
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (features, c1.weight, c1.bias, c2.weight, c2.bias)):
         out, idx = _SAVotes.apply(xyz.detach(), new_xyz.detach(), features, c1.weight, c1.bias, c2.weight, c2.bias,
                                   radius, nsample)
     else:
