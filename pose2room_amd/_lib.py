@@ -138,10 +138,10 @@ def prototypes(header_path=None):
     return _header()[0] if header_path is None else _parse(header_path)[0]
 
 
-def struct(name):
+def struct(name, header_path=None):
     """The ctypes.Structure of the header's `typedef struct { ... } name;` (a field named like a Python keyword gets a
-    trailing underscore: p2r_pw_rjob.in is `in_`)."""
-    return _header()[1][name]
+    trailing underscore: p2r_pw_rjob.in is `in_`).  header_path: an extension library's header instead."""
+    return _header()[1][name] if header_path is None else _parse(header_path)[1][name]
 
 
 def lib():

@@ -11,6 +11,10 @@ HBM once and each batch is one launch:
     on the host from the reference's generators (`dataloader.draw_augmentation`, one per sample in batch order) and
     yields batch dicts already on the device, equal bit for bit to what the host loader yields for the same seeds.
 
+A sample may come without votes: the store derives them on the device by the reference's contact rule
+(net_utils/vote_labels.py, csrc/vote_labels.hip), once at construction, or -- `votes='derive'`, the lean store, which
+keeps no votes -- for every gathered item inside the assemble launch (p2r_assemble_batch_lean).
+
 `transform_reference` is the NumPy mirror of the kernel's arithmetic (header comment of csrc/batch_assemble.hip).
 """
 import ctypes
@@ -24,6 +28,7 @@ from torch.utils.data import DataLoader, Dataset
 from torch.utils.data.distributed import DistributedSampler
 
 from .. import _lib
+from ..net_utils import vote_labels as vl
 from . import dataloader as dl
 
 ANGLES = (-np.pi, -0.5 * np.pi, 0, 0.5 * np.pi)     # the choices of draw_augmentation, in order
@@ -127,35 +132,56 @@ def floor_heights(joints):
 
 
 class DeviceSampleStore(object):
-    """Raw samples packed once into device memory (layout: include/p2r_hip.h, p2r_sample_store)."""
+    """Raw samples packed once into device memory (layout: include/p2r_hip.h, p2r_sample_store).
 
-    def __init__(self, samples, device=None, max_num_obj=10, joint_num=53, max_bytes=None):
-        """samples: iterable of (joints (T0, J, 3), votes (T0, J, 10), instances, name) as `read_sample_hdf5` returns
-        them plus a name; joints and votes float32.  max_bytes: refuse a store larger than this (default: half of the
-        device's memory)."""
+    votes='store' (default) keeps a (F, J, 10) vote array next to the joints.  A sample may come without one, as
+    `(joints, None, instances, name)`: its votes are then derived on the device at construction from its joints and
+    object boxes (net_utils/vote_labels.py, one p2r_vote_labels launch over all such samples).
+
+    votes='derive' is the lean store: it keeps no votes at all -- `self.votes is None` -- but the contact tables of
+    the samples (`self.contact`), and `assemble` derives the vote row of every gathered item in the launch
+    (p2r_assemble_batch_lean).  It holds 3 of 13 floats per (frame, joint), so 4.3 times as many samples fit under the
+    same max_bytes.  It accepts samples with or without a votes array and IGNORES a given one (after checking its type
+    and shape): its batches carry the votes the contact rule gives, whatever the array held."""
+
+    def __init__(self, samples, device=None, max_num_obj=10, joint_num=53, max_bytes=None, votes='store',
+                 contact_dist=None):
+        """samples: iterable of (joints (T0, J, 3), votes (T0, J, 10) or None, instances, name) as `read_sample_hdf5`
+        returns them plus a name; joints and votes float32.  max_bytes: refuse a store larger than this (default: half
+        of the device's memory).  contact_dist: the contact distance of derived votes (default: the config's
+        `dataset_config.contact_dist_thresh`, 1.0)."""
+        if votes not in ('store', 'derive'):
+            raise ValueError(f"DeviceSampleStore: votes must be 'store' or 'derive', got {votes!r}")
+        self.lean = votes == 'derive'
+        self.contact_dist = vl.default_contact_dist() if contact_dist is None else float(contact_dist)
         self.max_num_obj, self.joint_num = int(max_num_obj), int(joint_num)
         J, K = self.joint_num, self.max_num_obj
-        joints, votes, t0, names, floors, tables = [], [], [], [], [], []
+        joints, votes, t0, names, floors, tables, contact = [], [], [], [], [], [], []
         for i, (j, v, inst, name) in enumerate(samples):
-            j, v = np.asarray(j), np.asarray(v)
-            if j.dtype != np.float32 or v.dtype != np.float32:
-                raise ValueError(f"sample {i} ({name}): joints and votes must be float32, got {j.dtype} / {v.dtype}")
-            if j.ndim != 3 or j.shape[1:] != (J, 3) or v.shape != j.shape[:2] + (10,):
+            j, v = np.asarray(j), None if v is None else np.asarray(v)
+            if j.dtype != np.float32 or (v is not None and v.dtype != np.float32):
+                raise ValueError(f"sample {i} ({name}): joints and votes must be float32, got {j.dtype} / "
+                                 f"{getattr(v, 'dtype', None)}")
+            if j.ndim != 3 or j.shape[1:] != (J, 3) or (v is not None and v.shape != j.shape[:2] + (10,)):
                 raise ValueError(f"sample {i} ({name}): joints (T0, {J}, 3) and votes (T0, {J}, 10) expected, got "
-                                 f"{j.shape} / {v.shape}")
+                                 f"{j.shape} / {getattr(v, 'shape', None)}")
             if not 1 <= j.shape[0] <= MAX_T0:
                 raise ValueError(f"sample {i} ({name}): T0 = {j.shape[0]} frames, outside 1..{MAX_T0} (the "
                                  "reference's frame indices are uint16)")
             joints.append(j)
-            votes.append(v)
+            votes.append(None if self.lean else v)
             t0.append(j.shape[0])
             names.append(name)
             floors.append(floor_heights(j))
             tables.append(box_tables(inst, K))
+            contact.append(vl.contact_tables(inst, K, self.contact_dist, name=f"{i} ({name})")
+                           if self.lean or v is None else None)
         if not t0:
             raise ValueError("DeviceSampleStore: no samples")
         N, F = len(t0), int(sum(t0))
-        self.nbytes = F * J * 13 * 4 + N * (8 + 4 + 16 + N_VARIANTS * K * (24 + 8) + K * (12 + 4 + 8))
+        self.nbytes = F * J * (3 if self.lean else 13) * 4 + \
+            N * (8 + 4 + 16 + N_VARIANTS * K * (24 + 8) + K * (12 + 4 + 8)) + \
+            (vl.ContactBoxes.nbytes(N, K) if self.lean else 0)
         if max_bytes is not None and self.nbytes > max_bytes:
             raise MemoryError(f"DeviceSampleStore: {N} samples / {F} frames need {self.nbytes} bytes of device memory, "
                               f"above the cap of {max_bytes} bytes (max_bytes)")
@@ -170,20 +196,41 @@ class DeviceSampleStore(object):
         off[1:] = np.cumsum(t0)[:-1]
         put = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
         self.joints = put(np.concatenate(joints))
-        self.votes = put(np.concatenate(votes))
         self.frame_offset = put(off)
         self.n_frames = put(np.asarray(t0, np.int32))
+        self.contact = vl.ContactBoxes(contact, device) if self.lean else None
+        self.votes = None if self.lean else self._votes(votes, contact, off, t0, put)
         self.floor_height = put(np.asarray(floors, np.float64))
         self.box_center, self.box_heading, self.box_size, self.box_mask, self.box_cls = \
             [put(np.stack([t[k] for t in tables])) for k in range(5)]
         self.names = names
         self.T0 = np.asarray(t0)
-        self._c = _Store(joints=self.joints.data_ptr(), votes=self.votes.data_ptr(),
+        self._c = _Store(joints=self.joints.data_ptr(), votes=0 if self.lean else self.votes.data_ptr(),
                          frame_offset=self.frame_offset.data_ptr(), n_frames=self.n_frames.data_ptr(),
                          floor_height=self.floor_height.data_ptr(), box_center=self.box_center.data_ptr(),
                          box_heading=self.box_heading.data_ptr(), box_size=self.box_size.data_ptr(),
                          box_mask=self.box_mask.data_ptr(), box_cls=self.box_cls.data_ptr(), n_frames_total=F,
                          n_samples=N, J=J, K=K)
+
+    def _votes(self, votes, contact, off, t0, put):
+        """The packed (F, J, 10) votes: the given arrays copied, the missing ones derived on the device in ONE launch
+        over the pack of the samples that came without."""
+        missing = [i for i, v in enumerate(votes) if v is None]
+        if not missing:
+            return put(np.concatenate(votes))
+        boxes = vl.ContactBoxes([contact[i] for i in missing], self.device)
+        if len(missing) == len(votes):
+            return vl.vote_labels(self.joints, self.frame_offset, self.n_frames, boxes)
+        J = self.joint_num
+        out = put(np.concatenate([np.zeros((t, J, 10), np.float32) if v is None else v for v, t in zip(votes, t0)]))
+        sub_t0 = np.asarray([t0[i] for i in missing], np.int32)
+        sub_off = np.zeros(len(missing), np.int64)
+        sub_off[1:] = np.cumsum(sub_t0)[:-1]
+        derived = vl.vote_labels(torch.cat([self.joints[off[i]:off[i] + t0[i]] for i in missing]), put(sub_off),
+                                 put(sub_t0), boxes)
+        for i, o in zip(missing, sub_off):
+            out[off[i]:off[i] + t0[i]] = derived[o:o + t0[i]]
+        return out
 
     def __len__(self):
         return len(self.names)
@@ -245,8 +292,8 @@ _Store, _Out = _lib.struct('p2r_sample_store'), _lib.struct('p2r_batch_out')
 
 
 def assemble_batch(store, sel, aug, augment, use_height, num_frames, out):
-    """Thin binding of p2r_assemble_batch: sel (B, 3) i64 and aug (B, 10) f64 (or None) on the store's device, out the
-    dict of preallocated outputs.  Ids are the caller's to check (DeviceSampleStore.assemble does)."""
+    """Thin binding of p2r_assemble_batch (p2r_assemble_batch_lean for a lean store): sel (B, 3) i64 and aug (B, 10)
+    f64 (or None) on the store's device, out the dict of preallocated outputs.  Ids are the caller's to check (DeviceSampleStore.assemble does)."""
     tensors = [sel] + ([] if aug is None else [aug]) + list(out.values())
     if not all(torch.is_tensor(t) and t.is_cuda and t.device == store.device and t.is_contiguous() for t in tensors):
         raise RuntimeError(f"assemble_batch: every tensor must be contiguous on {store.device}")
@@ -254,6 +301,10 @@ def assemble_batch(store, sel, aug, augment, use_height, num_frames, out):
             (aug is not None and (aug.dtype != torch.float64 or aug.shape != (sel.shape[0], 10))):
         raise RuntimeError("assemble_batch: sel (B, 3) int64 and aug (B, 10) float64 expected")
     o = _Out(**{f[0]: out[f[0]].data_ptr() for f in _Out._fields_})
+    if store.lean:      # no stored votes: the launch derives them from the contact tables
+        vl.assemble_batch_lean(store.device, ctypes.byref(store._c), store.contact, int(sel.shape[0]), sel, aug,
+                               int(bool(augment)), int(bool(use_height)), int(num_frames), ctypes.byref(o))
+        return out
     _lib.launch("p2r_assemble_batch", store.device, ctypes.byref(store._c), int(sel.shape[0]), sel, aug, int(bool(augment)),
                 int(bool(use_height)), int(num_frames), ctypes.byref(o))
     return out

@@ -1,7 +1,8 @@
 """Sample loader throughput at bs=32, T=1024 (one GPU): the host loader against the device sample store.
 
     python tools/loader_throughput.py [--samples 384] [--t0 512 2048] [--batches 12] [--workers 0 4 15]
-                                      [--train-steps 20] [--only device] [--out profiles/loader_throughput.json]
+                                      [--train-steps 20] [--only device] [--lean] [--store-build 256 1024]
+                                      [--out profiles/loader_throughput.json]
 
 Raw samples are synthetic (p2rnet/synthetic.make_raw_sample, six boxes), T0 drawn uniformly from the --t0 range.
 Timed, with a device synchronisation at the end of each measurement, in 'train' mode (augmentation on):
@@ -10,6 +11,14 @@ Timed, with a device synchronisation at the end of each measurement, in 'train' 
                 the start of the epoch (worker start-up included) to the last batch
   device        P2RNet_device_dataloader over a DeviceSampleStore of the same samples (one launch per batch)
   assemble_ms   one DeviceSampleStore.assemble call at bs, T, median of --reps (host draws + launch, synchronised)
+  assemble_kernel_us  the assemble launch alone: --kernel-reps back-to-back launches between device events, launch
+                overhead included, per launch; with --lean also for the lean store (votes='derive': no stored votes,
+                p2r_assemble_batch_lean derives them in the launch) built from the same samples, plus that store's
+                bytes and its device-loader rate
+  store_build   with --store-build N T: the votes of N samples of T frames (six boxes each) by ONE p2r_vote_labels launch
+                (device events, median of --reps, and the achieved GB/s of its 12 bytes in + 40 bytes out per item)
+                against the NumPy mirror on the host for the same samples, and the wall time of building the store
+                from samples that bring no votes
   step_<loader> with --train-steps S: S train steps (Trainer.train_step) fed by the host loader with the most workers
                 and by the device loader, wall time per step
 """
@@ -42,6 +51,59 @@ def rate(loader, n_batches, dev):
     return n / (time.perf_counter() - t0)
 
 
+def kernel_us(store, dv, dl, bs, frames, reps):
+    """one assemble launch, microseconds: `reps` back-to-back launches on preallocated operands between device events"""
+    ids = list(range(bs))
+    out = store.assemble(ids, frames, True, [dl.draw_augmentation() for _ in ids])           # warm-up; the operands
+    tens = {k: v for k, v in out.items() if torch.is_tensor(v)}
+    sel = torch.zeros((bs, 3), dtype=torch.int64)
+    sel[:, 0] = torch.arange(bs)
+    sel[:, 1], sel[:, 2] = 1, 4 + 1
+    aug = torch.zeros((bs, 10), dtype=torch.float64)
+    aug[:, 0:9] = torch.from_numpy(dl.rot_y(dv.ANGLES[1]).reshape(9))
+    aug[:, 9] = 0.37
+    sel, aug = sel.to(store.device), aug.to(store.device)
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    dv.assemble_batch(store, sel, aug, True, False, frames, tens)
+    torch.cuda.synchronize()
+    start.record()
+    for _ in range(reps):
+        dv.assemble_batch(store, sel, aug, True, False, frames, tens)
+    end.record()
+    torch.cuda.synchronize()
+    return round(start.elapsed_time(end) * 1e3 / reps, 2)
+
+
+def store_build(n, frames, reps, dev, dv, make_raw_sample):
+    """p2r_vote_labels over n samples of `frames` frames against the NumPy mirror on the host"""
+    from pose2room_amd.net_utils import vote_labels as vl
+    samples = [make_raw_sample(frames, n_boxes=6, seed=1000 + i) for i in range(n)]
+    bare = [(j, None, inst, name) for j, _, inst, name in samples]
+    t = time.perf_counter()
+    mirror = [vl.vote_labels_reference(j, inst, 1.0) for j, _, inst, _ in samples]
+    mirror_s = time.perf_counter() - t
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    store = dv.DeviceSampleStore.from_samples(bare, device=dev)
+    torch.cuda.synchronize()
+    build_s = time.perf_counter() - t
+    equal = bool(torch.equal(store.votes.cpu().view(torch.int32), torch.from_numpy(np.concatenate(mirror)).view(torch.int32)))
+    boxes = vl.ContactBoxes([vl.contact_tables(inst, 10, 1.0) for _, _, inst, _ in samples], dev)
+    ms = []
+    for _ in range(reps + 2):
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record()
+        vl.vote_labels(store.joints, store.frame_offset, store.n_frames, boxes)
+        end.record()
+        torch.cuda.synchronize()
+        ms.append(start.elapsed_time(end))
+    k_ms = float(np.median(ms[2:]))
+    items = n * frames * 53
+    return {'samples': n, 'frames': frames, 'items': items, 'vote_labels_ms': round(k_ms, 4),
+            'vote_labels_GBps': round(items * 52 / (k_ms * 1e-3) / 1e9, 1), 'mirror_host_s': round(mirror_s, 2),
+            'store_from_bare_samples_s': round(build_s, 2), 'kernel_equals_mirror': equal}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--samples', type=int, default=384)
@@ -53,6 +115,10 @@ def main():
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--train-steps', type=int, default=0)
     ap.add_argument('--only', choices=['device'], default=None, help="device loader only (for a kernel trace)")
+    ap.add_argument('--kernel-reps', type=int, default=200)
+    ap.add_argument('--lean', action='store_true', help="also build and time the lean store (votes='derive')")
+    ap.add_argument('--store-build', type=int, nargs=2, default=None, metavar=('N', 'T'),
+                    help="time p2r_vote_labels over N samples of T frames against the NumPy mirror")
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -88,6 +154,20 @@ def main():
         torch.cuda.synchronize()
         ts.append((time.perf_counter() - t) * 1e3)
     res['assemble_ms'] = round(float(np.median(ts[2:])), 3)
+    res['assemble_kernel_us'] = {'full': kernel_us(store, dv, dl, a.bs, a.frames, a.kernel_reps)}
+    if a.lean:
+        t = time.perf_counter()
+        lean = dv.DeviceSampleStore.from_samples(samples, device=dev, votes='derive')
+        torch.cuda.synchronize()
+        res['lean'] = {'store_bytes': lean.nbytes, 'store_build_s': round(time.perf_counter() - t, 2),
+                       'bytes_ratio': round(lean.nbytes / store.nbytes, 4)}
+        leanl = dv.P2RNet_device_dataloader(cfg_for(0), 'train', lean)
+        rate(leanl.dataloader, 1, dev)
+        res['samples_per_s']['device_lean'] = round(rate(leanl.dataloader, nb, dev), 1)
+        res['assemble_kernel_us']['lean'] = kernel_us(lean, dv, dl, a.bs, a.frames, a.kernel_reps)
+        res['assemble_kernel_us']['full_again'] = kernel_us(store, dv, dl, a.bs, a.frames, a.kernel_reps)
+    if a.store_build:
+        res['store_build'] = store_build(a.store_build[0], a.store_build[1], a.reps, dev, dv, make_raw_sample)
     print(json.dumps(res), flush=True)
     if a.only == 'device':
         return
