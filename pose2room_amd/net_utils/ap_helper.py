@@ -133,10 +133,34 @@ def _to_host(tensors):
     return [o.numpy() for o in outs]
 
 
-def parse_predictions(est_data, gt_data, config_dict, return_device=False):
+PARSE_IMPLS = ('torch', 'kernel')
+
+
+def parse_predictions(est_data, gt_data, config_dict, return_device=False, impl=None, joints_repeat=1):
     """est_data: end_points of `P2RNet.generate`; gt_data: batch (needs 'input_joints' when
     remove_far_box).  Returns (eval_dict{'pred_mask' (B,K) uint8}, parsed{'pred_corners_3d'
-    (B,K,8,3) f64, 'sem_cls_probs' (B,K,C) f32, 'obj_prob' (B,K) f32, 'pred_sem_cls' (B,K) i64})."""
+    (B,K,8,3) f64, 'sem_cls_probs' (B,K,C) f32, 'obj_prob' (B,K) f32, 'pred_sem_cls' (B,K) i64}).
+    impl: None -> config_dict.get('parse_impl', 'torch'); 'torch' is the tensor math below, 'kernel' one launch of
+    p2r_parse_boxes for everything up to the NMS (parse_device.py).  joints_repeat = H ('kernel' only): est_data is an
+    H * B hypothesis-major stack and gt_data['input_joints'] holds the B rows of the batch."""
+    impl = config_dict.get('parse_impl', 'torch') if impl is None else impl
+    if impl not in PARSE_IMPLS:
+        raise ValueError(f"parse_predictions: impl must be one of {PARSE_IMPLS}, got {impl!r}")
+    if impl == 'kernel':
+        from . import parse_device
+        eval_dict, parsed = parse_device.parse_predictions_device(est_data, gt_data, config_dict, joints_repeat)
+        if return_device:
+            return eval_dict, parsed
+        sem = parsed['sem_cls_scores']
+        sampled = bool(config_dict['sample_cls'])
+        keep_h, corners_h, sem_h, obj_h, cls_h = _to_host(
+            [eval_dict['pred_mask'], parsed['pred_corners_3d'], torch.softmax(sem, dim=-1) if sampled else sem,
+             parsed['obj_prob'], parsed['pred_sem_cls']])
+        return ({'pred_mask': keep_h},
+                {'pred_corners_3d': corners_h, 'sem_cls_probs': sem_h if sampled else softmax(sem_h), 'obj_prob': obj_h,
+                 'pred_sem_cls': cls_h})
+    if joints_repeat != 1:
+        raise ValueError("parse_predictions: joints_repeat needs impl='kernel' (the tensor path takes expanded joints)")
     dataset_config = config_dict['dataset_config']
     pred_center = est_data['center'].detach()
     pred_size = torch.exp(est_data['size']).detach()

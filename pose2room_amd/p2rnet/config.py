@@ -52,7 +52,7 @@ _BASE = {
     'test': {'phase': 'full', 'batch_size': 1, 'use_cls_nms': False, 'use_3d_nms': True,
              'ap_iou_thresholds': [0.25, 0.5], 'remove_far_box': True, 'nms_iou': 0.10,
              'use_old_type_nms': False, 'per_class_proposal': True, 'conf_thresh': 0.05,
-             'multi_mode': False, 'sample_cls': False},
+             'multi_mode': False, 'sample_cls': False, 'parse_impl': 'torch'},
     'demo': {'phase': 'full'},
     'log': {'path': 'out/p2rnet', 'save_weight_step': 50, 'vis_step': 10, 'print_step': 10},     # p2rnet_train.yaml:55-59
 }
@@ -91,7 +91,15 @@ class P2RConfig:
                                 'nms_iou': t['nms_iou'], 'use_old_type_nms': t['use_old_type_nms'],
                                 'cls_nms': t['use_cls_nms'], 'per_class_proposal': t['per_class_proposal'],
                                 'conf_thresh': t['conf_thresh'], 'dataset_config': self.dataset_config,
-                                'multi_mode': t['multi_mode'], 'sample_cls': t['sample_cls']}
+                                'multi_mode': t['multi_mode'], 'sample_cls': t['sample_cls'],
+                                'parse_impl': self._parse_impl(t.get('parse_impl', 'torch'))}
+
+    @staticmethod
+    def _parse_impl(impl):
+        """test.parse_impl: 'torch' (tensor math, the default) or 'kernel' (net_utils/parse_device.py: one HIP launch)"""
+        if impl not in ('torch', 'kernel'):
+            raise ValueError(f"test.parse_impl must be 'torch' or 'kernel', got {impl!r}")
+        return impl
 
     def log_string(self, content):
         if self._logger is not None:

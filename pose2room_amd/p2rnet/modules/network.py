@@ -151,13 +151,19 @@ class P2RNet(BaseNetwork):
             xyz, features, end_points, H, ns, seed, central_tendency=central_tendency, return_draws=return_draws)
         B = end_points['aggregated_vote_xyz'].shape[0]
         joints = data['input_joints']
-        gt_stacked = {'input_joints': joints.unsqueeze(0).expand(H, *joints.shape).reshape(H * B, *joints.shape[1:])}
+        if self.cfg.eval_config.get('parse_impl', 'torch') == 'kernel':
+            # the kernel reads row n % B of the batch's joints for sample n of the stack: no H-fold copy
+            gt_stacked, repeat = {'input_joints': joints}, {'joints_repeat': H}
+        else:
+            gt_stacked = {'input_joints': joints.unsqueeze(0).expand(H, *joints.shape).reshape(H * B, *joints.shape[1:])}
+            repeat = {}
         if return_device:
-            eval_all, parsed_all = parse_predictions(stacked, gt_stacked, self.cfg.eval_config, return_device=True)
+            eval_all, parsed_all = parse_predictions(stacked, gt_stacked, self.cfg.eval_config, return_device=True,
+                                                     **repeat)
             out = {'end_points': end_points, 'pred_mask': eval_all['pred_mask'], **parsed_all}
             out.update({k: stacked[k] for k in ('center', 'size', 'heading')})
             return {k: v if k == 'end_points' else v.reshape(H, B, *v.shape[1:]) for k, v in out.items()}
-        eval_all, parsed_all = parse_predictions(stacked, gt_stacked, self.cfg.eval_config)
+        eval_all, parsed_all = parse_predictions(stacked, gt_stacked, self.cfg.eval_config, **repeat)
         gt_map = assembly_gt_map_cls(parse_groundtruths(data, self.cfg.eval_config)) if eval else None
         out = []
         for h in range(H):
