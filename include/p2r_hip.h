@@ -449,7 +449,9 @@ int p2r_embed3_weight_grad_lazy(int N, int L, const float *x, const float *g, co
  * output, fin [4][64] = mean, invstd, scale, shift of its BatchNorm); W [64][64] = the Conv1d weight [out][in].
  * Outputs: g_prev (N,64,L) = (W^T dz) where the input is positive else 0; sums [n_blocks][64][2] = per-workgroup
  * (sum g_prev, sum g_prev * (zp - mean) * invstd); dw_part [n_blocks][64][64] and db_part [n_blocks][64] (optional):
- * per-workgroup partials of dW [out][in] and of the bias gradient.  L % 64 == 0, tensors 16-byte aligned. */
+ * per-workgroup partials of dW [out][in] and of the bias gradient.  L % 64 == 0, tensors 16-byte aligned.
+ * n_blocks >= 1 is the caller's choice: at most N * L / 64 workgroups run, the partial rows beyond them are zeroed.
+ * N == 0: all n_blocks rows of sums, dw_part and db_part are zeroed, g_prev is empty and no kernel is launched. */
 int p2r_embed_layer_backward(int N, int L, const float *g, const float *z, const float *coef, const float *zp,
                              const float *fin, const float *W, float *g_prev, float *sums, int n_blocks,
                              float *dw_part, float *db_part, void *stream);

@@ -175,7 +175,8 @@ __global__ __launch_bounds__(256, 2) void embed_bwd_kernel(EbArgs p) {
 //   g_prev (N,64,L): (W^T dz) where the input is positive, else 0
 //   sums [n_blocks][64][2] = (sum g_prev, sum g_prev * (zp - mean) * invstd) per workgroup
 //   dw_part [n_blocks][64][64] (out, in), db_part [n_blocks][64] or NULL: per-workgroup partials of dW, db
-// L % 64 == 0, all tensors 16-byte aligned.
+// L % 64 == 0, all tensors 16-byte aligned.  Partial rows beyond the tile count are zeroed; N == 0: all n_blocks rows of
+// sums, dw_part and db_part are zeroed and no kernel is launched.
 extern "C" int p2r_embed_layer_backward(int N, int L, const float *g, const float *z, const float *coef, const float *zp,
                                         const float *fin, const float *W, float *g_prev, float *sums, int n_blocks,
                                         float *dw_part, float *db_part, void *stream) {
@@ -191,7 +192,7 @@ extern "C" int p2r_embed_layer_backward(int N, int L, const float *g, const floa
   // workgroups beyond the tile count would write nothing: every workgroup must own at least one tile for its partials
   // to be defined, so the caller's n_blocks is clamped here and the unused partial rows are zeroed
   int blocks = n_blocks;
-  if ((long long)blocks > a.tiles) blocks = (int)(a.tiles > 0 ? a.tiles : 1);
+  if ((long long)blocks > a.tiles) blocks = (int)a.tiles;          // N == 0: no workgroup, every partial row is zeroed
   if (blocks < n_blocks) {
     hipError_t e = hipMemsetAsync(sums + (size_t)blocks * 128, 0, (size_t)(n_blocks - blocks) * 128 * sizeof(float),
                                   p2r_stream(stream));
@@ -203,9 +204,7 @@ extern "C" int p2r_embed_layer_backward(int N, int L, const float *g, const floa
                          p2r_stream(stream));
     if (e != hipSuccess) return (int)e;
   }
-  if (N == 0) {
-    return (int)hipMemsetAsync(sums, 0, (size_t)blocks * 128 * sizeof(float), p2r_stream(stream));
-  }
+  if (N == 0) return P2R_OK;
   hipLaunchKernelGGL(embed_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, p2r_stream(stream), a);
   P2R_LAUNCH_CHECK();
   return P2R_OK;

@@ -98,6 +98,8 @@ class _EmbedMLP(Function):
         dev = x.device
         f32 = dict(dtype=torch.float32, device=dev)
         du = dout.contiguous()
+        if du.data_ptr() % 16 != 0:     # a contiguous view into the middle of a storage: the kernel loads 16-byte vectors
+            du = du.clone()
         P = _N_BLOCKS
         g2, g1 = torch.empty((B, 64, L), **f32), torch.empty((B, 64, L), **f32)
         sum2, sum1 = torch.empty((P, 64, 2), **f32), torch.empty((P, 64, 2), **f32)
