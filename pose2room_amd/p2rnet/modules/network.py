@@ -180,6 +180,38 @@ class P2RNet(BaseNetwork):
             out.append((ep, eval_dict, {k: v[sl] for k, v in parsed_all.items()}))
         return out
 
+    @torch.no_grad()
+    def predict_scenes(self, data, num_hypotheses=None, n_samples=None, seed=None, dump_threshold=None, contact=True,
+                       unique=True):
+        """What the reference's demo.py (`predict` + `visualize_step`, lines 204-266) gives the user of a trained model,
+        for the whole batch and on the device: data['input_joints'] (B,T,J,3|4) -> net_utils.scene_device.SceneBatch --
+        per sample the confident boxes as object nodes (centroid, R_mat, size, class), with `contact` the frame in which
+        the body is closest to each node (`dist_node2bbox`), with `unique` the frames without duplicates (`np.unique`
+        over the frames).  No ground truth is needed in `data`.
+          num_hypotheses: None -> one scene per sample from the deterministic heads (`generate_end_points`); H -> the H
+          hypotheses of `generate_hypotheses(return_device=True)` (n_samples, seed as there), an H * B stack that reads
+          the B joints rows in place.
+          dump_threshold: None -> cfg.config['generation']['dump_threshold'] when present, else 0.5.
+        From the end points on nothing leaves the device except the one check `parse_predictions` inherits from the
+        reference (`assert len(pick) > 0`); the SceneBatch crosses to the host when the caller asks it to."""
+        from ...net_utils import scene_device
+        from ...net_utils.ap_helper import parse_predictions
+        if dump_threshold is None:
+            dump_threshold = (self.cfg.config.get('generation') or {}).get('dump_threshold', 0.5)
+        joints = data['input_joints']
+        if num_hypotheses is None:
+            end_points = self.generate_end_points(data)
+            eval_dict, parsed = parse_predictions(end_points, data, self.cfg.eval_config, return_device=True)
+            H, out = 1, {'pred_mask': eval_dict['pred_mask'], **parsed}
+        else:
+            out = self.generate_hypotheses(data, num_hypotheses, n_samples=n_samples, seed=seed, return_device=True)
+            H = out['pred_mask'].shape[0]
+            out = {k: out[k].reshape(H * out[k].shape[1], *out[k].shape[2:])
+                   for k in ('pred_mask', 'pred_corners_3d', 'obj_prob', 'pred_sem_cls')}
+        return scene_device.scenes_from_parsed(out['pred_corners_3d'], out['obj_prob'], out['pred_mask'],
+                                               out['pred_sem_cls'], joints, dump_threshold, contact=contact,
+                                               unique=unique, num_hypotheses=H)
+
     def loss(self, pred_data, gt_data):
         if isinstance(pred_data, tuple):
             pred_data = pred_data[0]

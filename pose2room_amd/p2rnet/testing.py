@@ -4,7 +4,9 @@ Mirror of the reference's models/p2rnet/testing.py:16-50 (`Tester.test_step`: ge
 rank-averaged scalar dict, returns `(loss_dict, est_data)`) and test_epoch.py:10-76 (`test_func`,
 `test`: one `APCalculator` per IoU threshold of `cfg.config[mode]['ap_iou_thresholds']`, fed with
 `eval_dict['batch_pred_map_cls' / 'batch_gt_map_cls']` of every batch, loss meters synchronised over
-ranks at the end).  Visualisation / result dumping (testing.py:52-130) is file export and not mirrored.
+ranks at the end).  Rendering is out of scope; what the dump and the demo compute in front of it -- confident boxes as
+object nodes, unique frames, contact frames, the `pred_confident_nms_bbox.npz` layout -- is `P2RNet.predict_scenes`
+(net_utils/scene_device.py: SceneBatch.nodes / records / save_npz).
 """
 from time import time
 
