@@ -131,6 +131,14 @@ def floor_heights(joints):
     return float(np.percentile(y.astype(np.float64), 0.99)), float(np.percentile(y, 0.99))
 
 
+def store_nbytes(N, F, J, K, lean):
+    """Device bytes of a store of N samples / F frames: the packed frames, the per-sample rows and box tables, and the
+    contact tables of a lean store."""
+    return F * J * (3 if lean else 13) * 4 + \
+        N * (8 + 4 + 16 + N_VARIANTS * K * (24 + 8) + K * (12 + 4 + 8)) + \
+        (vl.ContactBoxes.nbytes(N, K) if lean else 0)
+
+
 class DeviceSampleStore(object):
     """Raw samples packed once into device memory (layout: include/p2r_hip.h, p2r_sample_store).
 
@@ -179,9 +187,7 @@ class DeviceSampleStore(object):
         if not t0:
             raise ValueError("DeviceSampleStore: no samples")
         N, F = len(t0), int(sum(t0))
-        self.nbytes = F * J * (3 if self.lean else 13) * 4 + \
-            N * (8 + 4 + 16 + N_VARIANTS * K * (24 + 8) + K * (12 + 4 + 8)) + \
-            (vl.ContactBoxes.nbytes(N, K) if self.lean else 0)
+        self.nbytes = store_nbytes(N, F, J, K, self.lean)
         if max_bytes is not None and self.nbytes > max_bytes:
             raise MemoryError(f"DeviceSampleStore: {N} samples / {F} frames need {self.nbytes} bytes of device memory, "
                               f"above the cap of {max_bytes} bytes (max_bytes)")
@@ -252,6 +258,70 @@ class DeviceSampleStore(object):
         kw.setdefault('max_num_obj', cfg.config['data']['max_gt_boxes'])
         kw.setdefault('joint_num', cfg.dataset_config.joint_num)
         return cls(gen(), **kw)
+
+    @classmethod
+    def from_recordings(cls, recordings, aug_indices=range(8), votes='store', device=None, max_num_obj=10,
+                        joint_num=53, max_bytes=None, contact_dist=None):
+        """The store of the samples that stage 3 of the reference's data preparation makes of raw recordings
+        (net_utils/sample_build.py: trim, reject, recentre, the variants `aug_indices`, the votes), built on the device:
+        no sample file, no host copy of a frame and no `floor_heights` -- the floors are p2r_floor_percentile's.  Equal,
+        tensor for tensor, to `DeviceSampleStore(build_reference(r).samples of every kept r, ...)`.  `recordings`: dicts
+        of joints (F, J, 3) float64, room_bbox, object_nodes and name.  `self.rejected` lists the (name, reason) of the
+        recordings that gave no sample, `self.kept` the indices of the others.
+        max_bytes (default: half of the device's memory) is checked before anything is allocated, against the size the
+        store would have if no frame were trimmed and no recording rejected: a store that would fit only after trimming
+        is refused.  The packed float64 copy of the recordings that lives during the build (24 bytes per input (frame,
+        joint)) is not counted; `self.nbytes` is the size of the finished store."""
+        from ..net_utils import sample_build as sb
+        if votes not in ('store', 'derive'):
+            raise ValueError(f"DeviceSampleStore: votes must be 'store' or 'derive', got {votes!r}")
+        device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        if device.type != 'cuda':
+            raise RuntimeError("DeviceSampleStore: the store lives on a GPU")
+        self = cls.__new__(cls)
+        self.lean = votes == 'derive'
+        self.contact_dist = vl.default_contact_dist() if contact_dist is None else float(contact_dist)
+        self.max_num_obj, self.joint_num = int(max_num_obj), int(joint_num)
+        J, K = self.joint_num, self.max_num_obj
+        recordings, aug_indices = list(recordings), list(aug_indices)
+        for i, r in enumerate(recordings):
+            if r['joints'].ndim != 3 or tuple(r['joints'].shape[1:]) != (J, 3):
+                raise ValueError(f"recording {i} ({r['name']}): joints (F, {J}, 3) expected, got "
+                                 f"{tuple(r['joints'].shape)}")
+        # what the build would allocate at most (no frame trimmed), before anything is allocated
+        N_max = len(recordings) * len(aug_indices)
+        F_max = sum(int(r['joints'].shape[0]) for r in recordings) * len(aug_indices)
+        size = lambda N, F: store_nbytes(N, F, J, K, self.lean)                         # noqa: E731
+        cap = torch.cuda.get_device_properties(device).total_memory // 2 if max_bytes is None else max_bytes
+        if size(N_max, F_max) > cap:
+            raise MemoryError(f"DeviceSampleStore: {N_max} samples / {F_max} frames need up to {size(N_max, F_max)} "
+                              f"bytes of device memory, above the cap of {cap} bytes (max_bytes)")
+        built = sb.build_samples(recordings, aug_indices, contact_dist=self.contact_dist, device=device,
+                                 votes=not self.lean, max_num_obj=K)
+        if not built.names:
+            raise ValueError(f"DeviceSampleStore: no samples (every recording was rejected: {built.rejected})")
+        N, F = len(built.names), int(built.joints.shape[0])
+        self.nbytes = size(N, F)
+        self.device = device
+        put = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)          # noqa: E731
+        self.joints, self.votes = built.joints, built.votes
+        self.frame_offset, self.n_frames = built.frame_offset, built.n_frames
+        self.contact = built.contact if self.lean else None
+        self.floor_height = built.floors
+        tables = [box_tables(inst, K) for inst in built.instances]
+        self.box_center, self.box_heading, self.box_size, self.box_mask, self.box_cls = \
+            [put(np.stack([t[k] for t in tables])) for k in range(5)]
+        self.names = built.names
+        self.kept, self.rejected = built.kept, built.rejected
+        per = len(built.names) // len(built.kept)
+        self.T0 = np.repeat([int(recordings[i]['joints'].shape[0]) - f for i, f in zip(built.kept, built.first)], per)
+        self._c = _Store(joints=self.joints.data_ptr(), votes=0 if self.lean else self.votes.data_ptr(),
+                         frame_offset=self.frame_offset.data_ptr(), n_frames=self.n_frames.data_ptr(),
+                         floor_height=self.floor_height.data_ptr(), box_center=self.box_center.data_ptr(),
+                         box_heading=self.box_heading.data_ptr(), box_size=self.box_size.data_ptr(),
+                         box_mask=self.box_mask.data_ptr(), box_cls=self.box_cls.data_ptr(), n_frames_total=F,
+                         n_samples=N, J=J, K=K)
+        return self
 
     def assemble(self, ids, num_frames, augment=False, draws=None, use_height=False):
         """One batch of samples `ids` -> the collate_fn dict on the store's device (sample_idx: list of names).
