@@ -106,8 +106,9 @@ __global__ __launch_bounds__(BN_THREADS) void bn_apply_kernel(int C, int L, int 
   const size_t base = (size_t)rowi * L;
   const int per = (((L + chunks - 1) / chunks) + 3) & ~3;   // multiple of 4: chunk starts stay 16-byte aligned
   const int lo = chunk * per, hi = min(L, lo + per);
+  // the mask leaves as uchar4: its row start must be 4-byte aligned too (as in both backward kernels)
   const bool vec = (((uintptr_t)(x + base) | (uintptr_t)(y + base) | (RES ? (uintptr_t)(res + base) : 0)) % 16 == 0) &&
-                   (lo % 4 == 0);
+                   (lo % 4 == 0) && (!(RELU && mask) || (base % 4 == 0 && (uintptr_t)mask % 4 == 0));
   int i = lo + threadIdx.x * 4;
   if (vec) {
     for (; i + 3 < hi; i += BN_THREADS * 4) {

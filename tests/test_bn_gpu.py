@@ -1,4 +1,7 @@
-"""GPU: fused BatchNorm(+residual)(+ReLU) kernels against torch.nn.BatchNorm2d."""
+"""GPU: fused BatchNorm(+residual)(+ReLU) kernels against torch.nn.BatchNorm2d at the shapes of a train step.
+
+The comparison against float64 -- per kernel stage under derived bounds, relu on and off, the chunked launches, every
+mask mode, and the op's gradients under the device's own gates -- is tests/test_bn_sweep_gpu.py."""
 import copy
 
 import pytest
