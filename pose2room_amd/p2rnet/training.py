@@ -183,6 +183,22 @@ class Trainer(object):
         self.net = net
         self.optimizer = optimizer
         self.device = device
+        # optimizer.clip_impl 'torch' | 'kernel' and optimizer.nonfinite 'ignore' | 'skip' | 'raise' (grad_guard.py): with
+        # the defaults there is no guard and train_step is what it was
+        spec = cfg.config.get('optimizer') or {}
+        clip_impl = spec.get('clip_impl', 'torch')
+        nonfinite = spec.get('nonfinite', 'ignore')
+        if clip_impl not in ('torch', 'kernel'):
+            raise ValueError(f"optimizer.clip_impl must be 'torch' or 'kernel', got {clip_impl!r}")
+        if nonfinite not in ('ignore', 'skip', 'raise'):
+            raise ValueError(f"optimizer.nonfinite must be 'ignore', 'skip' or 'raise', got {nonfinite!r}")
+        self.grad_guard = None
+        kernel_clip = clip_impl == 'kernel' and spec.get('clip_norm', -1) > 0
+        if kernel_clip or nonfinite != 'ignore':
+            from .grad_guard import GradGuard
+            # a guard that only watches leaves the clipping where it is: with torch, in front of it
+            self.grad_guard = GradGuard(net.named_parameters(), spec['clip_norm'] if kernel_clip else 0.0, nonfinite,
+                                        optimizer=optimizer)
 
     def to_device(self, data):
         for key in data:
@@ -204,10 +220,21 @@ class Trainer(object):
         fetch = _ScalarFetch(reduce_dict(loss))
         if loss['total'].requires_grad:
             loss['total'].backward()
+            if self.grad_guard is not None:
+                return self._guarded_step(fetch)
             max_norm = self.cfg.config['optimizer']['clip_norm']
             if max_norm > 0:
                 torch.nn.utils.clip_grad_norm_(self.net.parameters(), max_norm)
             self.optimizer.step()
+        return fetch.result()
+
+    def _guarded_step(self, fetch):
+        """clip + step of `train_step` through the guard (optimizer.clip_impl / optimizer.nonfinite); the loss dict and its
+        one host wait are the same, the guard's numbers come from `grad_guard.report()`"""
+        max_norm = self.cfg.config['optimizer']['clip_norm']
+        if max_norm > 0 and self.grad_guard.max_norm <= 0:      # clip_impl 'torch' under a guard that only watches
+            torch.nn.utils.clip_grad_norm_(self.net.parameters(), max_norm)
+        self.grad_guard.step(self.optimizer)
         return fetch.result()
 
     def eval_step(self, data):

@@ -1,0 +1,277 @@
+"""CPU: the contract of the gradient guard (p2rnet/grad_guard.py, csrc/grad_guard.hip) before any kernel is involved: the
+float64 mirror against torch's own clipping, the counting of non-finite entries, the hand-over that the guard relies on
+(`grad_scale` / `found_inf` of torch's fused AdamW, here on its CPU path), the ABI of include/p2r_grad_guard.h /
+libp2r_grad_guard.so, the argument checks of the entry points -- which return before any launch -- and the options of
+`Trainer`."""
+import ctypes
+import math
+import os
+import subprocess
+
+import pytest
+import torch
+from torch import nn
+
+from pose2room_amd import _lib
+from pose2room_amd.p2rnet import P2RConfig, default_config
+from pose2room_amd.p2rnet import grad_guard as gg
+from pose2room_amd.p2rnet.training import ModuleWrapper, Trainer
+from tests import grad_guard_cases as gc
+
+EINVAL = -22
+built = pytest.mark.skipif(not os.path.exists(gg.LIB_PATH), reason="libp2r_grad_guard.so is not built")
+
+
+def _torch_clip(grads, max_norm):
+    """torch.nn.utils.clip_grad_norm_ in float64 on the same list -> (norm, clipped list)"""
+    params = []
+    for g in grads:
+        if g is None:
+            continue
+        p = nn.Parameter(torch.zeros(g.shape, dtype=torch.float64))
+        p.grad = g.double().clone()
+        params.append(p)
+    norm = float(torch.nn.utils.clip_grad_norm_(params, max_norm)) if params else 0.0
+    it = iter(params)
+    return norm, [None if g is None else next(it).grad for g in grads]
+
+
+def _lists():
+    zero = [torch.zeros(5), None, torch.zeros(3, dtype=torch.float64), torch.zeros(0)]
+    return {'mixed': gc.mixed_list(0), 'small': gc.mixed_list(5, numels=(1, 3, 65), scale=1e-3), 'zero': zero,
+            'many': gc.many_small(1, count=40)}
+
+
+# ---- 1. the mirror against torch -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ['mixed', 'small', 'zero', 'many'])
+def test_reference_norm_is_torchs(name):
+    grads = _lists()[name]
+    assert any(g is None for g in grads)
+    ref = gg.grad_guard_reference(grads, 1.0)
+    norm, _ = _torch_clip(grads, 1.0)
+    assert gc.rel_close(ref['norm'], norm, 1e-12), (ref['norm'], norm)
+    assert ref['found'] == 0.0 and not any(ref['nonfinite']) and len(ref['sumsq']) == len(grads)
+    assert gc.rel_close(math.sqrt(sum(ref['sumsq'])), norm, 1e-12)
+
+
+@pytest.mark.parametrize("name", ['mixed', 'small', 'zero', 'many'])
+@pytest.mark.parametrize("divisor", [4.0, 0.25], ids=['clipped', 'norm-below-max'])
+def test_reference_clipping_is_torchs(name, divisor):
+    """`scale` is a float32 by contract and a float32 gradient is divided in float32, so the mirror equals torch's
+    float64 clipping to 1e-12 exactly where both roundings are exact: max_norm = (norm + 1e-6) / 4 makes the divisor 4
+    (a power of two), max_norm above the norm makes it exactly 1.  The roundings themselves are bounded in the next test."""
+    grads = _lists()[name]
+    norm, _ = _torch_clip(grads, 1.0)
+    max_norm = (norm + 1e-6) / divisor
+    ref = gg.grad_guard_reference(grads, max_norm)
+    assert ref['scale'] == max(divisor, 1.0)                      # exactly 1.0 when the norm is below max_norm
+    _, want = _torch_clip(grads, max_norm)
+    for got, w, g in zip(ref['clipped'], want, grads):
+        if g is None:
+            assert got is None
+            continue
+        assert got.dtype == g.dtype and got.shape == g.shape
+        err = (got.double() - w).abs()
+        assert bool((err <= 1e-12 * w.abs()).all())
+        if ref['scale'] == 1.0:
+            assert torch.equal(got, g)
+
+
+def test_reference_clipping_with_a_divisor_that_rounds():
+    """an arbitrary divisor: one rounding of scale to float32 and, for float32 gradients, one of the quotient -- 2^-23
+    relative to torch's float64 clipping, and 2^-24 + 2^-52 for the float64 gradients"""
+    grads = gc.mixed_list(0)
+    norm, _ = _torch_clip(grads, 1.0)
+    max_norm = norm / 13.0
+    ref = gg.grad_guard_reference(grads, max_norm)
+    assert ref['scale'] == float(torch.tensor((norm + 1e-6) / max_norm).float()) and 12.9 < ref['scale'] < 13.1
+    _, want = _torch_clip(grads, max_norm)
+    for got, w, g in zip(ref['clipped'], want, grads):
+        if g is not None:
+            rel = 2.0 ** -23 if g.dtype == torch.float32 else 2.0 ** -24 + 2.0 ** -50
+            assert bool(((got.double() - w).abs() <= rel * w.abs()).all())
+    assert gg.grad_guard_reference(grads, 0.0)['scale'] == 1.0 and gg.grad_guard_reference(grads, -1.0)['scale'] == 1.0
+
+
+# ---- 2. non-finite entries -------------------------------------------------------------------------------------------------
+def test_reference_counts_nonfinite_and_sums_the_rest():
+    grads, spots = gc.nonfinite_list()
+    ref = gg.grad_guard_reference(grads, 1.0)
+    assert ref['nonfinite'] == [0, 5, 0, 4, 0] and ref['found'] == 1.0
+    for i, g in enumerate(grads):
+        if g is None:
+            assert ref['sumsq'][i] == 0.0
+            continue
+        clean = g.double().clone()
+        for pos, _ in spots.get(i, []):
+            clean[pos] = 0.0
+        assert torch.isfinite(clean).all()
+        assert gc.rel_close(ref['sumsq'][i], float((clean * clean).sum()), 1e-15)
+    assert math.isfinite(ref['norm']) and ref['norm'] > 0
+    big = gg.grad_guard_reference(gc.magnitude_list(), 0.0)
+    assert gc.rel_close(big['sumsq'][0], 4096 * float(torch.tensor(1e30, dtype=torch.float32)) ** 2, 1e-15)
+    assert big['sumsq'][1] > 0 and big['sumsq'][2] == 1e-150 ** 2 and big['found'] == 0.0
+    with pytest.raises(ValueError, match="float32 or float64"):
+        gg.grad_guard_reference([torch.zeros(2, dtype=torch.float16)], 1.0)
+
+
+# ---- 3. the hand-over: grad_scale and found_inf of the fused AdamW ---------------------------------------------------------
+def _fused(params):
+    return torch.optim.AdamW(params, lr=1e-2, betas=(0.9, 0.99), eps=1e-8, weight_decay=0.01, fused=True)
+
+
+def _state(opt, params):
+    return [t.clone() for p in params for t in (p.detach(), opt.state[p]['exp_avg'], opt.state[p]['exp_avg_sq'],
+                                                opt.state[p]['step'])]
+
+
+def _same(a, b):
+    return len(a) == len(b) and all(x.dtype == y.dtype and torch.equal(x, y) for x, y in zip(a, b))
+
+
+def test_fused_adamw_takes_scale_and_found_inf():
+    g = torch.Generator().manual_seed(11)
+    init = [torch.randn(33, generator=g), torch.randn(17, generator=g, dtype=torch.float64)]
+    pa = [nn.Parameter(t.clone()) for t in init]
+    pb = [nn.Parameter(t.clone()) for t in init]
+    oa, ob = _fused(pa), _fused(pb)
+    assert gg.takes_found_inf(oa) and not gg.takes_found_inf(torch.optim.SGD(pb, lr=0.1))
+    assert not gg.takes_found_inf(torch.optim.AdamW(pb, lr=0.1, foreach=False))
+    for step in range(4):
+        grads = [torch.randn(33, generator=g) * 5, torch.randn(17, generator=g, dtype=torch.float64) * 5]
+        ref = gg.grad_guard_reference(grads, 1.0)
+        assert ref['scale'] > 10
+        for p, gr in zip(pa, grads):
+            p.grad = gr.clone()
+        oa.grad_scale = torch.tensor(ref['scale'], dtype=torch.float32)
+        oa.found_inf = torch.tensor(0.0, dtype=torch.float32)
+        oa.step()
+        del oa.grad_scale, oa.found_inf
+        for p, gr, c in zip(pa, grads, ref['clipped']):           # the quotient is written back
+            gc.assert_quotient(p.grad, gr, ref['scale'])
+            assert p.grad.dtype == gr.dtype
+        for p, q in zip(pb, pa):
+            p.grad = q.grad.clone()
+        ob.step()
+        assert _same(_state(oa, pa), _state(ob, pb)), step
+    before = _state(oa, pa)
+    for p in pa:
+        p.grad = torch.full_like(p, float('inf'))
+    oa.grad_scale = torch.tensor(2.0, dtype=torch.float32)
+    oa.found_inf = torch.tensor(1.0, dtype=torch.float32)
+    oa.step()
+    del oa.grad_scale, oa.found_inf
+    assert _same(_state(oa, pa), before)
+    assert [float(oa.state[p]['step']) for p in pa] == [4.0, 4.0]
+
+
+# ---- 4. the ABI ------------------------------------------------------------------------------------------------------------
+NAMES = ['p2r_grad_measure', 'p2r_grad_scale']
+
+
+def test_header_parses():
+    protos = _lib.prototypes(gg.HEADER_PATH)
+    assert sorted(protos) == _lib.declared_symbols(gg.HEADER_PATH) == NAMES
+    assert protos['p2r_grad_measure'].kinds == 'p' + 'i' + 'f' + 'ii' + 'p' * 10
+    assert protos['p2r_grad_scale'].kinds == 'pip'
+    assert all(p.has_stream and p.restype is ctypes.c_int for p in protos.values())
+    assert not set(protos) & set(_lib.declared_symbols())
+    E = gg.entry_type()
+    assert [f[0] for f in E._fields_] == ['data', 'numel', 'dtype'] and ctypes.sizeof(E) == 24
+    with open(gg.HEADER_PATH) as f:
+        text = f.read()
+    assert f"#define P2R_GG_CHUNK {gg.CHUNK} " in text and f"#define P2R_GG_GROUP {gg.GROUP} " in text
+    assert gc.CHUNK == gg.CHUNK and gc.NUMELS[-1] > 2 * gg.CHUNK
+    assert gg.n_chunks([0, 1, gg.CHUNK, gg.CHUNK + 1, 70001]) == 1 + 1 + 1 + 2 + 5
+
+
+@built
+def test_every_prototype_binds_and_library_exports_exactly_them():
+    protos = _lib.prototypes(gg.HEADER_PATH)
+    out = subprocess.run(["nm", "-D", "--defined-only", gg.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln and ln.split()[-1].startswith("p2r_")}
+    assert exported == set(protos)
+    for name, p in protos.items():
+        fn = getattr(gg.lib(), name)
+        assert fn.argtypes == p.argtypes and fn.restype is ctypes.c_int
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    assert not any(name in out for name in NAMES)
+
+
+_BUF = ctypes.create_string_buffer(64)          # non-NULL addresses; never read: every call below is refused first
+
+
+def _entries(*rows):
+    t = (gg.entry_type() * max(len(rows), 1))()
+    for e, (data, numel, dtype) in zip(t, rows):
+        e.data, e.numel, e.dtype = data, numel, dtype
+    return t
+
+
+@built
+def test_entry_points_refuse_bad_arguments():
+    l = gg.lib()
+    p8 = (ctypes.addressof(_BUF) + 7) & ~7
+    ok = _entries((p8, 5, 0), (None, 0, 1), (p8, gg.CHUNK + 1, 1))
+    good = dict(table=ok, n=3, max_norm=1.0, count_skips=1, n_chunks=4, part_sumsq=p8, part_count=p8, first_chunk=p8,
+                sumsq=p8, nonfinite=p8, norm=p8, scale=p8, found=p8, steps=p8, skipped=p8)
+    bad_tables = [_entries((p8, -1, 0)), _entries((p8, 5, 2)), _entries((None, 5, 0)), _entries((p8 + 4, 5, 1)),
+                  _entries((p8 + 2, 5, 0))]
+    cases = [dict(n=-1), dict(table=None), dict(n_chunks=3), dict(n_chunks=5), dict(max_norm=float('nan'))]
+    cases += [{k: None} for k in good if good[k] == p8]
+    cases += [dict(table=t, n=1, n_chunks=1) for t in bad_tables]
+    for bad in cases:
+        assert l.p2r_grad_measure(*{**good, **bad}.values(), None) == EINVAL, bad
+    assert l.p2r_grad_scale(ok, 3, None, None) == EINVAL
+    assert l.p2r_grad_scale(ok, -1, p8, None) == EINVAL
+    for t in bad_tables:
+        assert l.p2r_grad_scale(t, 1, p8, None) == EINVAL
+    # a table without elements: 0, and nothing launched (there is no device here to launch on)
+    assert l.p2r_grad_scale(None, 0, None, None) == 0
+    assert l.p2r_grad_scale(_entries((None, 0, 0), (p8, 0, 1)), 2, None, None) == 0
+
+
+def test_a_missing_library_is_an_error(monkeypatch):
+    monkeypatch.setattr(gg, 'LIB_PATH', os.path.join(os.path.dirname(gg.LIB_PATH), 'libp2r_grad_guard_absent.so'))
+    monkeypatch.setattr(gg, '_gg_lib', None)
+    with pytest.raises(_lib.P2RLibraryError, match="libp2r_grad_guard_absent.so is missing"):
+        gg.lib()
+
+
+# ---- 5. options ------------------------------------------------------------------------------------------------------------
+def _trainer(sgd=False, **spec):
+    cfg = P2RConfig(default_config('train', optimizer=spec), device='cpu')
+    net = ModuleWrapper(nn.Linear(3, 2))
+    opt = torch.optim.SGD(net.parameters(), lr=0.1) if sgd else torch.optim.AdamW(net.parameters(), lr=0.1)
+    return Trainer(cfg, net, opt, torch.device('cpu'))
+
+
+def test_trainer_options():
+    assert 'clip_impl' not in default_config('train')['optimizer'] and 'nonfinite' not in default_config('train')['optimizer']
+    assert _trainer().grad_guard is None
+    assert _trainer(clip_norm=1.0).grad_guard is None                       # clip_impl 'torch': today's path
+    assert _trainer(clip_impl='kernel').grad_guard is None                  # nothing to clip (clip_norm = -1)
+    with pytest.raises(ValueError, match="clip_impl"):
+        _trainer(clip_impl='hip')
+    with pytest.raises(ValueError, match="nonfinite"):
+        _trainer(nonfinite='zero')
+    with pytest.raises(ValueError, match="nonfinite='skip' needs"):
+        _trainer(sgd=True, nonfinite='skip')
+    with pytest.raises(RuntimeError, match=r"parameter module\.weight must be on a GPU"):
+        _trainer(clip_impl='kernel', clip_norm=1.0)
+    with pytest.raises(RuntimeError, match="must be on a GPU"):
+        _trainer(sgd=True, nonfinite='raise')
+
+
+def test_guard_refuses_what_it_cannot_take():
+    lin = nn.Linear(3, 2)
+    with pytest.raises(ValueError, match="nonfinite must be one of"):
+        gg.GradGuard(lin.named_parameters(), 1.0, 'zero')
+    with pytest.raises(ValueError, match="skip"):
+        gg.GradGuard(lin.named_parameters(), 1.0, 'skip', optimizer=torch.optim.AdamW(lin.parameters(), foreach=True))
+    with pytest.raises(RuntimeError, match="parameter weight must be on a GPU"):
+        gg.GradGuard(lin.named_parameters(), 1.0, 'ignore')
+    with pytest.raises(RuntimeError, match="gradient of w must be a GPU tensor"):
+        gg.measure([torch.zeros(3)], 1.0, names=['w'])
+    with pytest.raises(ValueError, match="no gradient and no device"):
+        gg.measure([None], 1.0)
