@@ -11,138 +11,34 @@
 // `inside` predicate must not see fused products).  Every loop is bounded at compile time or by a checked size, so
 // NaN and degenerate boxes cannot make a lane loop or write outside its own slots.
 #include "p2r_common.h"
+#include "obb_iou_body.h"
 
 #include "../../include/p2r_ap_eval.h"
 
 namespace {
 
 // ---- p2r_obb_iou ---------------------------------------------------------------------------------------------------------
+// The per-pair body (clip, shoelace, height overlap, volumes) lives in obb_iou_body.h, shared with consensus.hip.
 constexpr int IOU_LANES = 64;   // one wave per workgroup
-constexpr int IOU_CAP = 16;     // vertex slots per polygon (_CAP of box_util.py; a convex quad clipped by four
-                                // half-planes has <= 8 vertices, the slack absorbs rounding artefacts)
 constexpr int IOU_MAXK = 1024;
 constexpr int IOU_MAXG = 256;
-
-// box_util.py:37-38: p strictly left of the directed clip edge cp1 -> cp2
-__device__ __forceinline__ bool iou_inside(double c1x, double c1y, double c2x, double c2y, double px, double py) {
-  return (c2x - c1x) * (py - c1y) > (c2y - c1y) * (px - c1x);
-}
-
-// torch.minimum / torch.maximum / clamp(min=0) keep NaN; fmin / fmax would drop it
-__device__ __forceinline__ double iou_min(double a, double b) { return (a < b || a != a) ? a : b; }
-__device__ __forceinline__ double iou_max(double a, double b) { return (a > b || a != a) ? a : b; }
-
-// box_util.py:83-88 on corners 7,6,2,4: |c7-c6| |c6-c2| |c7-c4|
-__device__ __forceinline__ double iou_edge(const double *a, const double *b) {
-  const double dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
-  return sqrt(dx * dx + dy * dy + dz * dz);
-}
-
-// shoelace on a quad (box_util.py:17-20): 0.5 |sum x_i y_{i-1} - sum y_i x_{i-1}|
-__device__ __forceinline__ double iou_quad_area(const double (&x)[4], const double (&y)[4]) {
-  const double a = x[0] * y[3] + x[1] * y[0] + x[2] * y[1] + x[3] * y[2];
-  const double b = y[0] * x[3] + y[1] * x[0] + y[2] * x[1] + y[3] * x[2];
-  return 0.5 * fabs(a - b);
-}
 
 __global__ __launch_bounds__(IOU_LANES) void obb_iou_kernel(int P, int K, int G, const double *__restrict__ det,
                                                             const double *__restrict__ gt,
                                                             double *__restrict__ iou3d, double *__restrict__ iou2d) {
-  // the two vertex buffers of the clip, one column per lane: lane l touches only [..][..][..][l], consecutive lanes
-  // are consecutive 8-byte words (no bank conflict), and a slot index is checked against IOU_CAP before every store.
-  // A private array indexed by the running vertex count would live in scratch.
-  __shared__ double s_v[2][IOU_CAP][2][IOU_LANES];   // 32 KiB
+  __shared__ double s_v[2][IOU_CAP][2][IOU_LANES];   // 32 KiB: the two vertex buffers of the clip, one column per lane
   const int lane = threadIdx.x;
   const long long p = (long long)blockIdx.x * IOU_LANES + lane;
   if (p >= P) return;   // no barrier below: lanes are independent
   const int g = (int)(p % G);
   const long long bk = p / G;   // b * K + k
   const long long b = bk / K;
-  const double *c1 = det + bk * 24;
-  const double *c2 = gt + (b * G + g) * 24;
-
-  constexpr int FOOT[4] = {3, 2, 6, 7};   // counter-clockwise on (x, z) for any heading
-  double q1x[4], q1y[4], q2x[4], q2y[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    q1x[i] = c1[FOOT[i] * 3 + 0];
-    q1y[i] = c1[FOOT[i] * 3 + 2];
-    q2x[i] = c2[FOOT[i] * 3 + 0];
-    q2y[i] = c2[FOOT[i] * 3 + 2];
-    s_v[0][i][0][lane] = q1x[i];
-    s_v[0][i][1][lane] = q1y[i];
-  }
-
-  // Sutherland-Hodgman (box_util.py:22-69): subject = detection footprint, clip = ground-truth footprint
-  int cnt = 4;
-  double cp1x = q2x[3], cp1y = q2y[3];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int cur = j & 1, nxt = cur ^ 1;
-    const double cp2x = q2x[j], cp2y = q2y[j];
-    const int last = cnt > 0 ? cnt - 1 : 0;
-    double sx = s_v[cur][last][0][lane], sy = s_v[cur][last][1][lane];
-    int n = 0;   // vertices emitted; only the first IOU_CAP are stored
-    for (int i = 0; i < IOU_CAP; ++i) {
-      if (i < cnt) {
-        const double ex = s_v[cur][i][0][lane], ey = s_v[cur][i][1][lane];
-        const bool in_e = iou_inside(cp1x, cp1y, cp2x, cp2y, ex, ey);
-        const bool in_s = iou_inside(cp1x, cp1y, cp2x, cp2y, sx, sy);
-        if (in_e != in_s) {   // the edge s -> e crosses the clip line (box_util.py:40-46)
-          const double dcx = cp1x - cp2x, dcy = cp1y - cp2y;
-          const double dpx = sx - ex, dpy = sy - ey;
-          const double n1 = cp1x * cp2y - cp1y * cp2x;
-          const double n2 = sx * ey - sy * ex;
-          const double n3 = 1.0 / (dcx * dpy - dcy * dpx);
-          if (n < IOU_CAP) {
-            s_v[nxt][n][0][lane] = (n1 * dpx - n2 * dcx) * n3;
-            s_v[nxt][n][1][lane] = (n1 * dpy - n2 * dcy) * n3;
-          }
-          ++n;
-        }
-        if (in_e) {
-          if (n < IOU_CAP) {
-            s_v[nxt][n][0][lane] = ex;
-            s_v[nxt][n][1][lane] = ey;
-          }
-          ++n;
-        }
-        sx = ex;
-        sy = ey;
-      }
-    }
-    cnt = n < IOU_CAP ? n : IOU_CAP;
-    cp1x = cp2x;
-    cp1y = cp2y;
-  }
-
-  // shoelace over the cnt vertices left in buffer 0 (four passes: 0 -> 1 -> 0 -> 1 -> 0)
-  double inter = 0.0;
-  if (cnt >= 3) {
-    const double x0 = s_v[0][0][0][lane], y0 = s_v[0][0][1][lane];
-    double xi = x0, yi = y0, acc = 0.0;
-    for (int i = 0; i < IOU_CAP; ++i) {
-      if (i < cnt) {
-        const bool wrap = i + 1 >= cnt;
-        const int i1 = wrap ? 0 : i + 1;
-        const double xn = s_v[0][i1][0][lane], yn = s_v[0][i1][1][lane];
-        acc += xi * yn - yi * xn;
-        xi = xn;
-        yi = yn;
-      }
-    }
-    inter = 0.5 * fabs(acc);
-  }
-
-  const double a1 = iou_quad_area(q1x, q1y), a2 = iou_quad_area(q2x, q2y);
-  if (iou2d) iou2d[p] = inter / (a1 + a2 - inter);
-  const double ymax = iou_min(c1[7 * 3 + 1], c2[7 * 3 + 1]);
-  const double ymin = iou_max(c1[4 * 3 + 1], c2[4 * 3 + 1]);
-  const double h = iou_max(ymax - ymin, 0.0);
-  const double inter_vol = inter * h;
-  const double v1 = iou_edge(c1 + 21, c1 + 18) * iou_edge(c1 + 18, c1 + 6) * iou_edge(c1 + 21, c1 + 12);
-  const double v2 = iou_edge(c2 + 21, c2 + 18) * iou_edge(c2 + 18, c2 + 6) * iou_edge(c2 + 21, c2 + 12);
-  iou3d[p] = inter_vol / (v1 + v2 - inter_vol);
+  ObbFoot f1, f2;   // subject = detection footprint, clip = ground-truth footprint
+  obb_foot_load(det + bk * 24, f1);
+  obb_foot_load(gt + (b * G + g) * 24, f2);
+  double i2;
+  iou3d[p] = obb_pair_iou<IOU_LANES>(f1, f2, s_v, lane, i2);
+  if (iou2d) iou2d[p] = i2;
 }
 
 // ---- p2r_ap_match -------------------------------------------------------------------------------------------------------

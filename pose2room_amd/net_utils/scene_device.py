@@ -246,6 +246,13 @@ class SceneBatch(object):
         out = records_from_nodes(z['count'], z['inst_idx'], z['node_obbs'], z['node_cls'], self.K)
         return out if h is None else out[self.sample(0, h):self.sample(0, h) + self.B]
 
+    def consensus(self, iou_thresh=0.25, class_aware=True):
+        """-> consensus_device.ConsensusBatch: the H scenes of every sample merged into one by greedy-leader clustering of
+        their oriented boxes (two launches, nothing crosses to the host).  H = 1 is valid: every cluster has support 1
+        unless boxes of the one scene overlap."""
+        from . import consensus_device
+        return consensus_device.consensus_of(self, iou_thresh, class_aware)
+
     def save_npz(self, path, n):
         """Sample n in the layout of the reference's `%06d_pred_confident_nms_bbox.npz` (testing.py:132-134: obbs, cls,
         inst_idx), which its `read_pred` reads.  -> True, or False for a sample without nodes: the reference writes no

@@ -212,6 +212,16 @@ class P2RNet(BaseNetwork):
                                                out['pred_sem_cls'], joints, dump_threshold, contact=contact,
                                                unique=unique, num_hypotheses=H)
 
+    def predict_consensus(self, data, num_hypotheses, n_samples=None, seed=None, dump_threshold=None, iou_thresh=0.25,
+                          class_aware=True, contact=True, unique=True):
+        """One scene per sample out of `num_hypotheses` hypotheses: `predict_scenes(...)` with the same arguments, then
+        `SceneBatch.consensus(iou_thresh, class_aware)` -- the objects the hypotheses agree on, in how many of them each
+        appears and how far apart they put it (net_utils.consensus_device.ConsensusBatch; its `.scenes` is the
+        SceneBatch).  Nothing more crosses to the host than in `predict_scenes`."""
+        scenes = self.predict_scenes(data, num_hypotheses=num_hypotheses, n_samples=n_samples, seed=seed,
+                                     dump_threshold=dump_threshold, contact=contact, unique=unique)
+        return scenes.consensus(iou_thresh=iou_thresh, class_aware=class_aware)
+
     def loss(self, pred_data, gt_data):
         if isinstance(pred_data, tuple):
             pred_data = pred_data[0]
