@@ -253,6 +253,14 @@ class SceneBatch(object):
         from . import consensus_device
         return consensus_device.consensus_of(self, iou_thresh, class_aware)
 
+    def occupancy(self, grid, joints=None, gt=None, min_votes=None, owner=False):
+        """-> occupancy_device.OccupancyBatch: the voxels of `grid` (an occupancy_device.Grid) that the nodes of every
+        sample cover, the votes of the H hypotheses per voxel and the map of the voxels with min_votes (default
+        H // 2 + 1) or more; with joints (B,T,J,3|4) the body's voxels, with gt (a SceneBatch of the B ground-truth
+        scenes) the scene IoU.  At most 7 launches, nothing crosses to the host."""
+        from . import occupancy_device
+        return occupancy_device.occupancy_of(self, grid, joints=joints, gt=gt, min_votes=min_votes, owner=owner)
+
     def save_npz(self, path, n):
         """Sample n in the layout of the reference's `%06d_pred_confident_nms_bbox.npz` (testing.py:132-134: obbs, cls,
         inst_idx), which its `read_pred` reads.  -> True, or False for a sample without nodes: the reference writes no

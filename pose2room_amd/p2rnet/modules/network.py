@@ -222,6 +222,21 @@ class P2RNet(BaseNetwork):
                                      dump_threshold=dump_threshold, contact=contact, unique=unique)
         return scenes.consensus(iou_thresh=iou_thresh, class_aware=class_aware)
 
+    def predict_occupancy(self, data, grid, num_hypotheses=None, n_samples=None, seed=None, dump_threshold=None,
+                          min_votes=None, owner=False, body=True, with_gt=False):
+        """The predicted scenes as occupancy maps on `grid` (net_utils.occupancy_device.Grid): `predict_scenes(...)` with
+        the same arguments, then `SceneBatch.occupancy(grid, ...)` -- per sample and hypothesis the voxels its boxes
+        cover, per voxel the votes of the hypotheses, with `body` the voxels the input joints fall into and with
+        `with_gt` (data must hold the labels) the ground-truth map and the scene IoU
+        (net_utils.occupancy_device.OccupancyBatch; its `.scenes` is the SceneBatch).  Nothing more crosses to the host
+        than in `predict_scenes`."""
+        from ...net_utils import occupancy_device
+        scenes = self.predict_scenes(data, num_hypotheses=num_hypotheses, n_samples=n_samples, seed=seed,
+                                     dump_threshold=dump_threshold, contact=False, unique=False)
+        gt = occupancy_device.scenes_from_labels(data, self.cfg) if with_gt else None
+        return scenes.occupancy(grid, joints=data['input_joints'] if body else None, gt=gt, min_votes=min_votes,
+                                owner=owner)
+
     def loss(self, pred_data, gt_data):
         if isinstance(pred_data, tuple):
             pred_data = pred_data[0]
