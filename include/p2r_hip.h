@@ -525,7 +525,8 @@ int p2r_gemm_nt_256(int nb, int L, int split, const float *A, const float *B, fl
  *           BatchNorm + ReLU), or tr[0][c] * x + tr[1][c] * x2 + tr[2][c] (tr_mode 2: the BatchNorm-backward form;
  *           x = masked gradient, x2 = saved conv output).  tr rows are `tr_ld` floats apart.
  *           x_ctot = channels of the tensor x (and x2) points INTO (the pointer is already offset to this job's
- *           first channel); x_nlc != 0: (B, L, x_ctot) memory, k % 4 == 0 then.
+ *           first channel); x_nlc != 0: (B, L, x_ctot) memory: with k % 4 == 0 and x_ctot % 4 == 0 the channels are
+ *           loaded 16 bytes at a time, any other k or x_ctot takes scalar loads (same result).
  *   w     : w_t == 0: [rows][k] row-major (a Conv1d weight, forward); w_t != 0: [k][rows] (the same weight read
  *           transposed: data gradient).
  *   bias  : [rows] or NULL.
@@ -595,7 +596,9 @@ int p2r_pw_reduce(int njobs, const p2r_pw_rjob *jobs, void *stream);
  * (f64 == 0) or f64 (the heading head, whose `mu` is a float64 parameter); log_sigma, dlog_sigma f32; eps == NULL:
  * the mixture mean (get_mean, mdn.py:85-99).  pi (B, G, L) f32 optional output.  D <= 4.
  * Backward: dpred (B, L, D) -> dlogit (B, G, L) f32 (inside a tensor of dlogit_ctot channels), dmu [G][D],
- * dlog_sigma [G][D]; one workgroup per (head, component). */
+ * dlog_sigma [G][D]; one workgroup per (head, component).
+ * B == 0: the forward returns P2R_OK and writes nothing; the backward returns P2R_EINVAL (dmu / dlog_sigma are sums
+ * over the columns: their zeros would have to be written, and callers never run a backward without a forward's batch). */
 typedef struct p2r_mix_head {
   const float *logit, *log_sigma;
   const void *mu, *eps, *dpred;

@@ -206,6 +206,10 @@ __global__ __launch_bounds__(256) void vote_finish_grad_kernel(int S, const floa
 // inds[b, s] = argmin_t |cum[b, t] - target[b, s]| (first minimum), exactly the fp32 expression torch evaluates
 // (`torch.argmin(torch.abs(cum.unsqueeze(-1) - target.unsqueeze(1)), dim=1)`) without the (B, T, S) difference tensor:
 // the cumulative arc length of a sample sits in LDS, a thread walks it for one target.
+// NaN is where the two part: torch.argmin returns the first NaN; here a NaN distance at t >= 1 never wins (d < best is
+// false) and a NaN distance at t = 0 is never displaced (index 0).  The model needs a valid frame index, not torch's
+// choice: its `cum` is a cumulative sum starting at 0 and its targets are multiples of cum's last entry, so a NaN in the
+// input makes every distance NaN and both rules return frame 0.
 __global__ __launch_bounds__(256) void nearest_prefix_kernel(int T, int S, const float *__restrict__ cum,
                                                              const float *__restrict__ target,
                                                              long long *__restrict__ inds) {
@@ -220,7 +224,7 @@ __global__ __launch_bounds__(256) void nearest_prefix_kernel(int T, int S, const
   int arg = 0;
   for (int t = 1; t < T; ++t) {
     const float d = fabsf(row[t] - tg);
-    if (d < best) { best = d; arg = t; }          // strict: the first minimum wins, like argmin; NaN never wins
+    if (d < best) { best = d; arg = t; }          // strict: the first minimum wins, like argmin; a NaN d never does
   }
   inds[(size_t)b * S + s] = arg;
 }

@@ -94,8 +94,10 @@ def add_broadcast_last(a, b):
 
 def nearest_prefix(cum, target):
     """cum (B,T), target (B,S) f32 on the GPU -> (B,S) int64: first index t minimising |cum[b,t] - target[b,s]| -- what
-    `torch.argmin(torch.abs(cum.unsqueeze(-1) - target.unsqueeze(1)), dim=1)` returns, in one launch and without the
-    (B,T,S) tensor."""
+    `torch.argmin(torch.abs(cum.unsqueeze(-1) - target.unsqueeze(1)), dim=1)` returns for NaN-free inputs, in one launch
+    and without the (B,T,S) tensor.  With NaN the two differ: torch.argmin returns the first NaN distance; here a NaN
+    distance at t >= 1 never wins and one at t = 0 is never displaced (index 0) -- always a valid frame.  For the model's
+    inputs (a cumulative sum from 0, targets derived from its last entry) a NaN makes both return frame 0."""
     cum, target = cum.contiguous(), target.contiguous()
     B, T = cum.shape
     S = target.shape[1]

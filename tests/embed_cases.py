@@ -232,7 +232,7 @@ def bn_bwd_coef_ref(S1, S2, fin, M, train):
         coef = torch.stack([scale, b, c1 + c2])
         E = torch.stack([zero, gamma(3) * b.abs(), gamma(3) * c1.abs() + gamma(5) * c2.abs()])
     else:
-        coef, E = torch.stack([scale, zero, zero]), torch.zeros(3, C, dtype=torch.float64)
+        coef, E = torch.stack([scale, zero, zero]), torch.zeros(3, scale.numel(), dtype=torch.float64)
     return {"coef": (coef, E), "dgamma": (S2, gamma(1) * S2.abs()), "dbeta": (S1, gamma(1) * S1.abs())}
 
 
