@@ -18,7 +18,8 @@ the same way, under the name `name + '_%d' % a`.
   * `build_reference`   the NumPy mirror of that contract, one recording
   * `floor_reference`   the two `np.percentile(y, 0.99)` mirrors the floor kernel computes
   * `recording_scan`, `floor_percentile`   the entry points on tensors
-  * `build_samples`     recordings -> packed device tensors (joints, votes, frame_offset, n_frames, floors)
+  * `build_samples`     recordings -> packed device tensors (joints, votes, frame_offset, n_frames, floors); with
+                        `repair=` the recordings' missing joints are filled on the device first (recording_repair.py)
 
 The host computes the per-box rows, O(boxes), with the reference's own expressions; every per-frame pass is a kernel.
 Between the scan and the build the host reads back `first` and `status`, 8 bytes per recording, to size the output.
@@ -36,6 +37,7 @@ from . import vote_labels as vl
 
 MAX_FRAMES, MAX_J = 65535, 256          # P2R_SB_MAX_FRAMES / P2R_SB_MAX_J of include/p2r_sample_build.h
 NEVER_IN_ROOM, NEAR_NO_OBJECT = "never in the room", "near no object"
+UNREPAIRABLE = "not finite after the repair"        # only with build_samples(repair=..., on_unrepairable='skip')
 STATUS_NO_ROOM, STATUS_NO_OBJECT, STATUS_NON_FINITE = 1, 2, 4
 
 FLIP = np.array([[0, 0, 1], [0, 1, 0], [1, 0, 0]])           # swaps x and z
@@ -265,6 +267,33 @@ class Recordings(object):
                              n_frames=self.n_frames.data_ptr(), n_frames_total=int(self.joints.shape[0]), R=self.R,
                              J=self.J, max_frames=int(self.frames.max()))
 
+    @classmethod
+    def from_packed(cls, joints, frame_offset, n_frames, frames):
+        """The Recordings of tensors that are packed on one GPU already: joints (F_total, J, 3) f64, frame_offset (R,)
+        i64 ascending, n_frames (R,) i32, and `frames`, the HOST's copy of the frame counts (R,) -- nothing is read
+        back.  The tensors are kept, not copied."""
+        frames = np.asarray(frames, np.int32)
+        R = int(frames.shape[0]) if frames.ndim == 1 else 0
+        for name, t, dtype, shape in (('joints', joints, torch.float64, None), ('frame_offset', frame_offset, torch.int64, (R,)),
+                                      ('n_frames', n_frames, torch.int32, (R,))):
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.is_contiguous()
+                    and t.device == joints.device and (shape is None or tuple(t.shape) == shape)):
+                raise RuntimeError(f"Recordings.from_packed: {name} must be a contiguous {dtype} GPU tensor"
+                                   + (f" of shape {shape}" if shape else "") + " (no CPU fallback)")
+        if joints.dim() != 3 or joints.shape[2] != 3 or not 1 <= joints.shape[1] <= MAX_J or joints.shape[0] < 1:
+            raise ValueError(f"Recordings.from_packed: joints (F_total, J, 3) with J in 1..{MAX_J} expected, got "
+                             f"{tuple(joints.shape)}")
+        if R < 1 or frames.min() < 1 or frames.max() > MAX_FRAMES or int(frames.sum(dtype=np.int64)) > joints.shape[0]:
+            raise ValueError(f"Recordings.from_packed: frames must hold R >= 1 counts in 1..{MAX_FRAMES} that sum to at "
+                             f"most the {joints.shape[0]} packed frames, got {frames.tolist()}")
+        self = cls.__new__(cls)
+        self.joints, self.frames, self.frame_offset, self.n_frames = joints, frames, frame_offset, n_frames
+        self.R, self.J, self.device = R, int(joints.shape[1]), joints.device
+        self.c = _Recordings(joints=joints.data_ptr(), frame_offset=frame_offset.data_ptr(),
+                             n_frames=n_frames.data_ptr(), n_frames_total=int(joints.shape[0]), R=R, J=self.J,
+                             max_frames=int(frames.max()))
+        return self
+
 
 def recording_scan(rec, room, objects, origin_joint):
     """p2r_recording_scan: rec a Recordings, room (R, 15) f64 tensor (`room_row` per recording), objects the
@@ -331,11 +360,23 @@ room of every kept recording, contact = the ContactBoxes of the samples (K = max
 
 
 def build_samples(recordings, aug_indices=range(8), contact_dist=None, device=None, votes=True, max_num_obj=None,
-                  origin_joint=None):
+                  origin_joint=None, repair=None, on_unrepairable='raise'):
     """Recordings (module docstring) -> BuiltSamples: the samples of every kept recording, variant by variant in the
     order of aug_indices, packed on `device` (default: the current GPU).  contact_dist and origin_joint default to the
     config's; max_num_obj = the box slots of `contact` (default: the largest object count).  Raises ValueError, naming
-    the recording, for a coordinate that is not finite.  Three launches and one read-back of 8 bytes per recording."""
+    the recording, for a coordinate that is not finite.  Three launches and one read-back of 8 bytes per recording.
+
+    repair: a `recording_repair.RepairSpec` conditions the recordings in front of the scan (missing joints filled over
+    short gaps, optionally low-passed: net_utils/recording_repair.py); its statistics ride in the same read-back, 24
+    bytes per recording then.  What is still not finite afterwards raises the same ValueError (on_unrepairable='raise')
+    or rejects the recording with the reason UNREPAIRABLE ('skip').  The result is then a `RepairedSamples`: the same
+    tuple with the attribute `repair`, the statistics (R, 4) of every recording given."""
+    if on_unrepairable not in ('raise', 'skip'):
+        raise ValueError(f"build_samples: on_unrepairable must be 'raise' or 'skip', got {on_unrepairable!r}")
+    if repair is not None:
+        from . import recording_repair as rr
+        if not isinstance(repair, rr.RepairSpec):
+            raise TypeError(f"build_samples: repair must be a RepairSpec or None, got {type(repair).__name__}")
     cfg = _config()
     contact_dist = float(cfg.contact_dist_thresh) if contact_dist is None else float(contact_dist)
     origin_joint = int(cfg.origin_joint_id if origin_joint is None else origin_joint)
@@ -352,15 +393,25 @@ def build_samples(recordings, aug_indices=range(8), contact_dist=None, device=No
     objects = vl.ContactBoxes([vl.contact_tables(enlarged_nodes(r['object_nodes'], contact_dist), K, 0.0,
                                                  name=r['name']) for r in recordings], device)
     room = torch.from_numpy(np.stack([room_row(r['room_bbox']) for r in recordings])).to(device)
-    first_d, status_d = recording_scan(rec, room, objects, origin_joint)
-    first, status = torch.stack([first_d, status_d]).cpu().numpy()          # the one crossing: 8 bytes per recording
+    repair_stats = None
+    if repair is not None:
+        rec, _, stats_d = rr.repair_packed(rec, repair)
+        first_d, status_d = recording_scan(rec, room, objects, origin_joint)
+        # still the one crossing: first, status and the four statistics of every recording
+        back = torch.cat([torch.stack([first_d, status_d], 1), stats_d], 1).cpu().numpy()
+        first, status, repair_stats = back[:, 0], back[:, 1], np.ascontiguousarray(back[:, 2:])
+    else:
+        first_d, status_d = recording_scan(rec, room, objects, origin_joint)
+        first, status = torch.stack([first_d, status_d]).cpu().numpy()      # the one crossing: 8 bytes per recording
     bad = [r['name'] for r, s in zip(recordings, status) if s & STATUS_NON_FINITE]
-    if bad:
+    if bad and (repair is None or on_unrepairable == 'raise'):
         raise ValueError(f"build_samples: recording {bad[0]} has a coordinate that is not finite"
                          + (f" (and {len(bad) - 1} more: {bad[1:]})" if len(bad) > 1 else ""))
-    kept = [i for i, s in enumerate(status) if not s & (STATUS_NO_ROOM | STATUS_NO_OBJECT)]
-    rejected = [(r['name'], NEVER_IN_ROOM if s & STATUS_NO_ROOM else NEAR_NO_OBJECT)
-                for r, s in zip(recordings, status) if s & (STATUS_NO_ROOM | STATUS_NO_OBJECT)]
+    drop = STATUS_NO_ROOM | STATUS_NO_OBJECT | STATUS_NON_FINITE           # the last only with on_unrepairable='skip'
+    kept = [i for i, s in enumerate(status) if not s & drop]
+    rejected = [(r['name'], UNREPAIRABLE if s & STATUS_NON_FINITE else NEVER_IN_ROOM if s & STATUS_NO_ROOM
+                 else NEAR_NO_OBJECT) for r, s in zip(recordings, status) if s & drop]
+    done = (lambda built: built) if repair is None else (lambda built: rr.RepairedSamples(built, repair_stats))  # noqa: E731
     names, instances, tables, plan, shifts = [], [], [], [], []
     for i in kept:
         r, shift = recordings[i], floor_shift(recordings[i]['room_bbox'])
@@ -373,10 +424,10 @@ def build_samples(recordings, aug_indices=range(8), contact_dist=None, device=No
             shifts.append(shift)
     empty = lambda *shape, dtype: torch.zeros(shape, dtype=dtype, device=device)       # noqa: E731
     if not plan:
-        return BuiltSamples(empty(0, rec.J, 3, dtype=torch.float32),
-                            empty(0, rec.J, 10, dtype=torch.float32) if votes else None,
-                            empty(0, dtype=torch.int64), empty(0, dtype=torch.int32), empty(0, 2, dtype=torch.float64),
-                            names, instances, kept, rejected, [], None)
+        return done(BuiltSamples(empty(0, rec.J, 3, dtype=torch.float32),
+                                 empty(0, rec.J, 10, dtype=torch.float32) if votes else None,
+                                 empty(0, dtype=torch.int64), empty(0, dtype=torch.int32),
+                                 empty(0, 2, dtype=torch.float64), names, instances, kept, rejected, [], None))
     plan = np.asarray(plan, np.int64)
     out_off = np.zeros(len(plan), np.int64)
     out_off[1:] = np.cumsum(plan[:, 3])[:-1]
@@ -389,5 +440,5 @@ def build_samples(recordings, aug_indices=range(8), contact_dist=None, device=No
                                      torch.from_numpy(np.stack(shifts)).to(device), F_out, contact, votes=votes)
     n_frames = cols[3].contiguous()
     floors = floor_percentile(joints, out_offset, n_frames, max_frames=int(plan[:, 3].max()))
-    return BuiltSamples(joints, out_votes, out_offset, n_frames, floors, names, instances, kept, rejected,
-                        [int(first[i]) for i in kept], contact)
+    return done(BuiltSamples(joints, out_votes, out_offset, n_frames, floors, names, instances, kept, rejected,
+                             [int(first[i]) for i in kept], contact))

@@ -261,7 +261,7 @@ class DeviceSampleStore(object):
 
     @classmethod
     def from_recordings(cls, recordings, aug_indices=range(8), votes='store', device=None, max_num_obj=10,
-                        joint_num=53, max_bytes=None, contact_dist=None):
+                        joint_num=53, max_bytes=None, contact_dist=None, repair=None, on_unrepairable='raise'):
         """The store of the samples that stage 3 of the reference's data preparation makes of raw recordings
         (net_utils/sample_build.py: trim, reject, recentre, the variants `aug_indices`, the votes), built on the device:
         no sample file, no host copy of a frame and no `floor_heights` -- the floors are p2r_floor_percentile's.  Equal,
@@ -271,7 +271,10 @@ class DeviceSampleStore(object):
         max_bytes (default: half of the device's memory) is checked before anything is allocated, against the size the
         store would have if no frame were trimmed and no recording rejected: a store that would fit only after trimming
         is refused.  The packed float64 copy of the recordings that lives during the build (24 bytes per input (frame,
-        joint)) is not counted; `self.nbytes` is the size of the finished store."""
+        joint)) is not counted; `self.nbytes` is the size of the finished store.
+        repair, on_unrepairable: `build_samples`' -- a `RepairSpec` fills the missing joints of the recordings on the
+        device first (net_utils/recording_repair.py); `self.repair` then holds the statistics (R, 4) of every recording
+        given, None without."""
         from ..net_utils import sample_build as sb
         if votes not in ('store', 'derive'):
             raise ValueError(f"DeviceSampleStore: votes must be 'store' or 'derive', got {votes!r}")
@@ -297,7 +300,8 @@ class DeviceSampleStore(object):
             raise MemoryError(f"DeviceSampleStore: {N_max} samples / {F_max} frames need up to {size(N_max, F_max)} "
                               f"bytes of device memory, above the cap of {cap} bytes (max_bytes)")
         built = sb.build_samples(recordings, aug_indices, contact_dist=self.contact_dist, device=device,
-                                 votes=not self.lean, max_num_obj=K)
+                                 votes=not self.lean, max_num_obj=K, repair=repair, on_unrepairable=on_unrepairable)
+        self.repair = getattr(built, 'repair', None)
         if not built.names:
             raise ValueError(f"DeviceSampleStore: no samples (every recording was rejected: {built.rejected})")
         N, F = len(built.names), int(built.joints.shape[0])
