@@ -196,7 +196,11 @@ int p2r_nms3d(int B, int K, int stride, const double *boxes,
  * stats_partial, when not NULL, receives [N * ceil(T / (384 / V))][64][2]: per
  * workgroup (sum, sum of squares) of z per channel -- the batch statistics the
  * BatchNorm after the graph conv needs (tcn.0, stgcn_layers.py:400), taken from the
- * accumulators instead of a second pass over z. */
+ * accumulators instead of a second pass over z.
+ * N == 0 (every graph-conv and temporal-conv entry point of this header): P2R_OK.  Outputs of shape (N, ...) are empty
+ * and nothing is launched; *n_partials is 0; a per-workgroup partial buffer whose shape does not depend on N
+ * (dw_partial, colsum_partial, dcoef_partial, dbias_partial: [n_blocks][...]) is ZERO-FILLED, a sum over nothing, since
+ * its caller adds the rows up whatever N is. */
 int p2r_stgcn_gcn_forward(int N, int T, int V, int K, const int *Lk_host,
                           const float *x, const float *W, const uint8_t *nbr,
                           const float *coef, const float *bias_cv, float *z,
@@ -234,7 +238,10 @@ int p2r_stgcn_gcn2_forward(int N, int T, int V, int K, int ltot, const float *x,
  * (P2R_EINVAL otherwise: use the second generation).
  * stats_partial of a forward-statistics launch (no bwd_*) is [*n_partials][64][3] = (count, mean, M2) per workgroup
  * and channel -- sums about a pivot per (wave, row), merged with their counts at the end of the kernel, so the
- * variance survives |mean| >> std (p2r_bn_finalize width 3); with bwd_* it is [*n_partials][64][2] as before. */
+ * variance survives |mean| >> std (p2r_bn_finalize width 3); with bwd_* it is [*n_partials][64][2] as before.
+ * Refused with P2R_EINVAL, nothing written: V != 53, K != 11, form other than 0 / 1, T % 16 != 0, a misaligned x / z /
+ * addend / bwd_u (16 bytes) or bwd_mask (4 bytes), bwd_u / bwd_mask / bwd_fin given in part, or given without
+ * stats_partial or with form 0.  N == 0: P2R_OK, *n_partials = 0, nothing launched. */
 unsigned long long p2r_stgcn_gcn3_signature(int form);
 int p2r_stgcn_gcn3_forward(int N, int T, int V, int K, int ltot, int form, const float *x, const float *Wp,
                            const float *coef, const float *bias_cv, const float *addend, float *z,
@@ -247,7 +254,9 @@ int p2r_stgcn_gcn3_forward(int N, int T, int V, int K, int ltot, int form, const
  * arriving at the previous block's output and addend_mask = that block's ReLU mask: the residual-branch gradient
  * dout * mask, which the BatchNorm-backward pass then does not have to write.  bwd_u / bwd_mask / bwd_fin and
  * stats_partial as in p2r_stgcn_gcn3_forward: all given = with the BatchNorm-backward sums epilogue, all NULL = plain
- * (the caller runs p2r_bn_bwd_reduce itself, e.g. on another stream under the gradient kernels that follow). */
+ * (the caller runs p2r_bn_bwd_reduce itself, e.g. on another stream under the gradient kernels that follow).
+ * "Non-zero" is any of the byte values 1 .. 255, here and for bwd_mask.  addend or addend_mask NULL, addend_mask not
+ * 4-byte aligned: P2R_EINVAL. */
 int p2r_stgcn_gcn3_data_gradient_masked_addend(int N, int T, int V, int K, int ltot, const float *x,
                                                const float *Wp, const float *coef, const float *addend,
                                                const unsigned char *addend_mask, float *z, float *stats_partial,
@@ -259,8 +268,9 @@ int p2r_stgcn_gcn3_data_gradient_masked_addend(int N, int T, int V, int K, int l
  *   dcoef[lofs_k + j][v] = sum over (n, t, c) of (W_k . x)[c, t, v] * dz[c, t, w_j(k, v)]
  * x, dz (N,64,T,53); Wp [K][4][4][64][4] = the forward planes in kernel order; dcoef_partial
  * [n_blocks][ltot][53] per-workgroup sums, summed over the leading axis by the caller.  T % 16 == 0, dz 16-byte
- * aligned (P2R_EINVAL otherwise: use p2r_stgcn_gcn_coef_grad).  Replaces the autograd of the einsum
- * w.r.t. `A * edge_importance` (stgcn_layers.py:62-65, stgcn.py:134). */
+ * aligned (P2R_EINVAL otherwise: use p2r_stgcn_gcn_coef_grad).  Padded slots of the tables come out exactly 0; an entry
+ * whose current coefficient is zero still gets its gradient.  N == 0: dcoef_partial is zero-filled.  Replaces the autograd
+ * of the einsum w.r.t. `A * edge_importance` (stgcn_layers.py:62-65, stgcn.py:134). */
 int p2r_stgcn_gcn3_coef_grad(int N, int T, int V, int K, int ltot, const float *x, const float *dz,
                              const float *Wp, int n_blocks, float *dcoef_partial, void *stream);
 
@@ -271,8 +281,9 @@ int p2r_stgcn_gcn3_coef_grad(int N, int T, int V, int K, int ltot, const float *
  * (aggregation on the gradient side through the row lists; coef [ltot][53] = row coefficient table), summed over the
  * leading axis and transposed by the caller (p2r_sum_leading, tr64).  colsum_partial (optional) [n_blocks][64][53] =
  * per-workgroup sums of dz over samples and frames (gradient of the bias table).  T % 4 == 0, x and dz 16-byte
- * aligned (P2R_EINVAL otherwise: use p2r_stgcn_gcn_weight_grad).  Replaces the autograd of the 1x1 conv weight
- * (stgcn_layers.py:57-67). */
+ * aligned (P2R_EINVAL otherwise: use p2r_stgcn_gcn_weight_grad).  A workgroup without a tile (n_blocks > tiles) writes
+ * zeros.  N == 0: dw_partial and colsum_partial are zero-filled, as p2r_stgcn_gcn3_coef_grad does.  Replaces the autograd
+ * of the 1x1 conv weight (stgcn_layers.py:57-67). */
 int p2r_stgcn_gcn3_weight_grad(int N, int T, int V, int K, int ltot, const float *x, const float *dz,
                                const float *coef, int n_blocks, float *dw_partial, float *colsum_partial,
                                void *stream);
@@ -285,7 +296,7 @@ int p2r_stgcn_gcn3_weight_grad(int N, int T, int V, int K, int ltot, const float
  * aggregation on the gradient side, where the row lists leave more (plane, joint-group) units
  * empty to skip.  colsum_partial, when not NULL, receives [n_blocks][64][V] partial sums over
  * samples and frames of the `dz` argument (colsum_of_x = 0) or of the `x` argument
- * (colsum_of_x != 0): the gradient of the bias table bias_cv, read from the same tiles. */
+ * (colsum_of_x != 0): the gradient of the bias table bias_cv, read from the same tiles.  N == 0: both are zero-filled. */
 int p2r_stgcn_gcn_weight_grad(int N, int T, int V, int K, const int *Lk_host,
                               const float *x, const float *dz,
                               const uint8_t *nbr, const float *coef,
@@ -302,7 +313,8 @@ int p2r_stgcn_gcn_weight_grad(int N, int T, int V, int K, const int *Lk_host,
  * coef ([sum_k Lk][V] floats or NULL) only tells real slots (non-zero) from padding (zero): pass a
  * 0/1 table of the adjacency pattern rather than the current coefficients, since a real entry whose
  * coefficient is momentarily zero still has a gradient; with NULL every slot 0 and every later slot
- * holding a non-zero joint counts as real and no unit is skipped. */
+ * holding a non-zero joint counts as real and no unit is skipped.  Padded slots come out exactly 0.  N == 0:
+ * dcoef_partial is zero-filled. */
 int p2r_stgcn_gcn_coef_grad(int N, int T, int V, int K, const int *Lk_host,
                             const float *x, const float *dz, const float *Wt,
                             const uint8_t *nbr, const float *coef, int n_blocks,
@@ -375,7 +387,10 @@ int p2r_stgcn_tconv_forward(int N, int T, int V, int taps, const float *x, const
 
 /* weight gradient: dw_partial [n_blocks][64 c][64 ci][taps] (the layout of the Conv2d weight; summed by the caller) of
  * sum_{n,t,w} dout[n,c,t,w] * h[n,ci,t+p-(taps-1)/2,w] with h as above; dbias_partial,
- * when not NULL, [n_blocks][64] = per-workgroup sums of dout per channel (bias gradient). */
+ * when not NULL, [n_blocks][64] = per-workgroup sums of dout per channel (bias gradient).  The ReLU gate of h is
+ * fmaf(x, scale, shift) > 0, one rounding, in every kernel that forms it (forward, data-gradient epilogue, weight
+ * gradient, p2r_bn_bwd_reduce / p2r_bn_bwd_apply with relu = 2).  V <= 64 with one tap, V <= 57 with three (the two
+ * tiles of 4 and 6 frames must fit the 160 KB of LDS; P2R_EINVAL beyond).  N == 0: both partials are zero-filled. */
 int p2r_stgcn_tconv_weight_grad(int N, int T, int V, int taps, const float *x, const float *scale,
                                 const float *shift, const float *dout, int n_blocks,
                                 float *dw_partial, float *dbias_partial, void *stream);
@@ -386,7 +401,7 @@ int p2r_stgcn_tconv_weight_grad(int N, int T, int V, int taps, const float *x, c
  *   dz[n,c,t,w] = scale[c] * ((x * scale[c] + shift[c] > 0 ? dh : 0) - m1[c] - (x - mean[c]) * invstd[c] * m2[c])
  * dh = gradient w.r.t. the BatchNorm-ReLU output (the data gradient of the convolution); fin [4][64] = mean, invstd,
  * scale, shift (p2r_bn_finalize); m12 [2][64] = m1, m2 (rows 2, 3 of p2r_bn_bwd_finalize; zeros in evaluation mode).
- * dz must not alias x or dh. */
+ * dz must not alias x or dh.  N == 0: dz is empty, the partials are zero-filled. */
 int p2r_stgcn_tconv_weight_grad_dz(int N, int T, int V, int taps, const float *x, const float *fin,
                                    const float *dout, const float *dh, const float *m12, float *dz, int n_blocks,
                                    float *dw_partial, float *dbias_partial, void *stream);

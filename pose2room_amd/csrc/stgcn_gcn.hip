@@ -616,10 +616,14 @@ __device__ __forceinline__ void dc_reduce(const floatx4_t (&h)[4], const float4 
   // sum over the four lane groups in the VALU (gfx950 lane swaps), then one LDS atomic per column
 #pragma unroll
   for (int j = 0; j < L; ++j) part[j] = rows4_sum(part[j]);
+  // Lr is the longest real list among the n-tile's 16 columns: a slot below it may still be padding of THIS column's
+  // shorter list (it holds joint 0 and is no link) and must stay exactly zero
   if (g == 0) {
 #pragma unroll
-    for (int j = 0; j < L; ++j)
-      if (j < Lr) atomicAdd(dcs_row + j * V, part[j]);
+    for (int j = 0; j < L; ++j) {
+      const int mark = trow[(j < Lr ? j : 0) * V].y;              // 1 real, 0 padding, 2 joint 0 without coefficients
+      if (j < Lr && (mark == 1 || (mark == 2 && j == 0))) atomicAdd(dcs_row + j * V, part[j]);
+    }
   }
 }
 
@@ -845,7 +849,12 @@ extern "C" int p2r_stgcn_gcn_weight_grad(int N, int T, int V, int K, const int *
   const int ltot = gcn_fill_params(p, T, V, K, Lk_host, DW_F);
   if (ltot < 0) return ltot;
   if (K > DW_SETS * DW_PL || N < 0 || n_blocks < 1) return P2R_EINVAL;
-  if (N == 0) return P2R_OK;
+  if (N == 0) {      // a sum over nothing: zero partials (the caller sums them whatever N is)
+    hipError_t e = hipMemsetAsync(dw_partial, 0, (size_t)n_blocks * K * GC_C * GC_C * sizeof(float), p2r_stream(stream));
+    if (e == hipSuccess && colsum_partial)
+      e = hipMemsetAsync(colsum_partial, 0, (size_t)n_blocks * GC_C * V * sizeof(float), p2r_stream(stream));
+    return (int)e;
+  }
   // DW_SETS plane sets with balanced gather work (longest lists first, greedy)
   DwSets sets;
   int cnt[DW_SETS] = {0}, load[DW_SETS] = {0}, order[GC_MAXK];
@@ -892,7 +901,8 @@ extern "C" int p2r_stgcn_gcn_coef_grad(int N, int T, int V, int K, const int *Lk
   const int ltot = gcn_fill_params(p, T, V, K, Lk_host, GC_NP / (V > 0 ? V : 1));
   if (ltot < 0) return ltot;
   if (N < 0 || n_blocks < 1) return P2R_EINVAL;
-  if (N == 0) return P2R_OK;
+  if (N == 0)        // a sum over nothing: zero partials
+    return (int)hipMemsetAsync(dcoef_partial, 0, (size_t)n_blocks * ltot * V * sizeof(float), p2r_stream(stream));
   const size_t lds = (size_t)16 * DC_ROW4 * sizeof(float4) + (size_t)ltot * V * (sizeof(int2) + sizeof(float)) +
                      2 * (DC_THREADS / 64) * GC_NT16 * sizeof(int);
   if (lds > 160 * 1024) return P2R_EINVAL;

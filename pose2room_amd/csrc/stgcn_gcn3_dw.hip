@@ -266,13 +266,19 @@ __global__ __launch_bounds__(W3_NW * 64, 2) void gcn3_dw_kernel(W3Params p, cons
 //   dw_partial [n_blocks][K][64][64]: per-workgroup partial of dW_k TRANSPOSED, [k][ci][c]; the caller sums over the
 //     leading axis and transposes (p2r_sum_leading with tr64).
 //   colsum_partial (optional) [n_blocks][64][53]: per-workgroup sums of dz over samples and frames.
-// T % 4 == 0 and x, dz 16-byte aligned (P2R_EINVAL otherwise: use p2r_stgcn_gcn_weight_grad).
+// T % 4 == 0 and x, dz 16-byte aligned (P2R_EINVAL otherwise: use p2r_stgcn_gcn_weight_grad).  N == 0: both partials
+// are zero-filled.
 extern "C" int p2r_stgcn_gcn3_weight_grad(int N, int T, int V, int K, int ltot, const float *x, const float *dz,
                                           const float *coef, int n_blocks, float *dw_partial, float *colsum_partial,
                                           void *stream) {
   if (N < 0 || T <= 0 || V != W3_V || K != G3_K || ltot <= 0 || n_blocks < 1) return P2R_EINVAL;
   if (T % W3_F != 0 || T > (1 << 20) || ((uintptr_t)x % 16) != 0 || ((uintptr_t)dz % 16) != 0) return P2R_EINVAL;
-  if (N == 0) return P2R_EINVAL;
+  if (N == 0) {      // a sum over nothing: zero partials, as p2r_stgcn_gcn3_coef_grad leaves them
+    hipError_t e = hipMemsetAsync(dw_partial, 0, (size_t)n_blocks * K * 64 * 64 * sizeof(float), p2r_stream(stream));
+    if (e == hipSuccess && colsum_partial)
+      e = hipMemsetAsync(colsum_partial, 0, (size_t)n_blocks * 64 * V * sizeof(float), p2r_stream(stream));
+    return (int)e;
+  }
   W3Params p;
   p.T = T; p.ltot = ltot;
   p.tiles_per_seq = T / W3_F;

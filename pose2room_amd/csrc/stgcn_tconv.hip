@@ -523,13 +523,21 @@ static int tconv_dw_launch(int N, int T, int V, const float *x, const float *sca
   return P2R_OK;
 }
 
+// N == 0 of the weight-gradient entry points: a sum over nothing, zero partials (the caller sums them whatever N is)
+static int tconv_dw_zero(int taps, int n_blocks, float *dw_partial, float *dbias_partial, void *stream) {
+  hipError_t e = hipMemsetAsync(dw_partial, 0, (size_t)n_blocks * TC_C * TC_C * taps * sizeof(float), p2r_stream(stream));
+  if (e == hipSuccess && dbias_partial)
+    e = hipMemsetAsync(dbias_partial, 0, (size_t)n_blocks * TC_C * sizeof(float), p2r_stream(stream));
+  return (int)e;
+}
+
 // dw_partial [n_blocks][64 c][64 ci][taps] and (optional) dbias_partial [n_blocks][64] = row sums of dout,
 // both summed over the leading axis by the caller.
 extern "C" int p2r_stgcn_tconv_weight_grad(int N, int T, int V, int taps, const float *x, const float *scale,
                                            const float *shift, const float *dout, int n_blocks,
                                            float *dw_partial, float *dbias_partial, void *stream) {
   if (N < 0 || T <= 0 || V <= 0 || V > 64 || n_blocks < 1 || (taps != 1 && taps != 3)) return P2R_EINVAL;
-  if (N == 0) return P2R_OK;
+  if (N == 0) return tconv_dw_zero(taps, n_blocks, dw_partial, dbias_partial, stream);
   // 20 columns per frame, one tap: the 64 -> 64 layers of the position-embedding MLP (stgcn.py:46-63, knn = 20).  A
   // 4-frame tile is 20 reduction steps there -- less work than the staging and the two barriers around it -- so this
   // shape gets 12-frame tiles (60 steps, 123 KB of LDS) and its own fully unrolled instance.
@@ -553,7 +561,7 @@ extern "C" int p2r_stgcn_tconv_weight_grad_dz(int N, int T, int V, int taps, con
                                               const float *dout, const float *dh, const float *m12, float *dz,
                                               int n_blocks, float *dw_partial, float *dbias_partial, void *stream) {
   if (N < 0 || T <= 0 || V != 53 || taps != 3 || n_blocks < 1 || !fin || !dh || !m12 || !dz) return P2R_EINVAL;
-  if (N == 0) return P2R_OK;
+  if (N == 0) return tconv_dw_zero(taps, n_blocks, dw_partial, dbias_partial, stream);
   return tconv_dw_launch<3, 53, TW_F, true>(N, T, V, x, fin + 128, fin + 192, dout, n_blocks, dw_partial, dbias_partial,
                                             stream, dh, fin, m12, dz);
 }
@@ -566,7 +574,7 @@ extern "C" int p2r_stgcn_tconv_weight_grad_dz_amax(int N, int T, int V, int taps
   if (N < 0 || T <= 0 || V != 53 || taps != 3 || n_blocks < 1 || !fin || !dh || !m12 || !dz || !amax_bits) return P2R_EINVAL;
   hipError_t e = hipMemsetAsync(amax_bits, 0, sizeof(unsigned), p2r_stream(stream));
   if (e != hipSuccess) return (int)e;
-  if (N == 0) return P2R_OK;
+  if (N == 0) return tconv_dw_zero(taps, n_blocks, dw_partial, dbias_partial, stream);
   return tconv_dw_launch<3, 53, TW_F, true, true>(N, T, V, x, fin + 128, fin + 192, dout, n_blocks, dw_partial,
                                                   dbias_partial, stream, dh, fin, m12, dz, amax_bits);
 }

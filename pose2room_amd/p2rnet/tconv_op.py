@@ -248,7 +248,8 @@ class _BNReLUTConv(Function):
 
 
 def supported(z, bn, conv):
-    return (z.is_cuda and z.dtype == torch.float32 and z.dim() == 4 and z.shape[1] == 64 and z.shape[3] <= 64
+    # 57 joints: the most whose 4- and 6-frame tiles fit the LDS of p2r_stgcn_tconv_weight_grad with three taps
+    return (z.is_cuda and z.dtype == torch.float32 and z.dim() == 4 and z.shape[1] == 64 and z.shape[3] <= 57
             and conv.in_channels == 64 and conv.out_channels == 64 and tuple(conv.kernel_size) == (3, 1)
             and tuple(conv.stride) == (1, 1) and tuple(conv.padding) == (1, 0) and tuple(conv.dilation) == (1, 1)
             and conv.groups == 1 and bn_op.supported(z, bn))
