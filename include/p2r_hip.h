@@ -747,7 +747,9 @@ int p2r_bn_bwd_apply_amax(int N, int C, int L, const float *dy, const unsigned c
 /* p2r_bn_apply with ReLU (res / mask optional) that also leaves the range word of y. */
 int p2r_bn_apply_amax(int N, int C, int L, const float *x, const float *scale, const float *shift, const float *res,
                       float *y, unsigned char *mask, unsigned *amax_bits, void *stream);
-/* p2r_stgcn_tconv_weight_grad_dz that also leaves the range word of dz. */
+/* p2r_stgcn_tconv_weight_grad_dz that also leaves the range word of dz: *amax_bits is cleared by every accepted call and
+ * then holds the float bits of max |dz| of THIS call (0 for N == 0); dz, dw_partial and dbias_partial are bit for bit
+ * those of p2r_stgcn_tconv_weight_grad_dz.  amax_bits NULL: P2R_EINVAL. */
 int p2r_stgcn_tconv_weight_grad_dz_amax(int N, int T, int V, int taps, const float *x, const float *fin,
                                         const float *dout, const float *dh, const float *m12, float *dz, int n_blocks,
                                         float *dw_partial, float *dbias_partial, unsigned *amax_bits, void *stream);
@@ -762,7 +764,11 @@ int p2r_stgcn_tconv_weight_grad_dz_amax(int N, int T, int V, int taps, const flo
  *         is used at scale 1, clamped to fp16's largest finite value)
  *   stats_partial [*n_partials][64][3] = (count, mean, M2) per workgroup and channel (forward) or [*n_partials][64][2]
  *         (bwd_z / bwd_fin given: the two sums of the BatchNorm + ReLU backward); *n_partials = N * T / chunk with
- *         chunk = the longest of 64 / 32 / 16 frames dividing T; out == NULL queries it. */
+ *         chunk = the longest of 64 / 32 / 16 frames dividing T; out == NULL queries it.
+ * Refused with P2R_EINVAL, nothing written (*n_partials included): V != 53, T % 16 != 0, T > 2^20, scale without shift
+ * or shift without scale, bwd_z and bwd_fin given in part, bwd_z with scale or without stats_partial, Wh not 16-byte
+ * aligned.  With out != NULL a NULL Wh or winv is refused after *n_partials is set, no tensor written.  x and out need
+ * no alignment.  N == 0: P2R_OK, *n_partials = 0, nothing launched. */
 int p2r_stgcn_tconvh_forward(int N, int T, int V, const float *x, const float *scale, const float *shift,
                              const void *Wh, const float *winv, const float *bias, float *out, float *stats_partial,
                              int *n_partials, const float *bwd_z, const float *bwd_fin, const unsigned *x_amax,
@@ -780,7 +786,12 @@ int p2r_stgcn_tconvh_forward(int N, int T, int V, const float *x, const float *s
  *   winv  device float 2^-S_w;  coef [ltot][53] f32 as for p2r_stgcn_gcn3_forward (the kernel scales it by 2^S_x)
  *   x_amax / dz_amax: range word of the operand tensor (NULL: scale 1)
  *   stats_partial [*n_partials][64][3] (optional) as p2r_stgcn_gcn3_forward's forward statistics.
- * The data gradient adds `addend` (NULL: nothing) where the bytes of `addend_mask` are non-zero (NULL: everywhere). */
+ * The data gradient adds `addend` (NULL: nothing) where the bytes of `addend_mask` are non-zero (NULL: everywhere).
+ * Refused with P2R_EINVAL, nothing written: V != 53, K != 11, ltot other than the schedule's (47 column-list rows for the
+ * forward, 62 row-list rows for the data gradient), T % 16 != 0, T > 2^19 (16 channel rows of a sample as a 32-bit byte
+ * offset), x / z / addend / Wh not 16-byte aligned, addend_mask not 4-byte aligned, addend_mask without addend.
+ * *n_partials = min(N T / 16, 256); z == NULL queries it; with z != NULL a NULL Wh, winv or coef is refused after
+ * *n_partials is set, no tensor written.  N == 0: P2R_OK, *n_partials = 0, nothing launched (as p2r_stgcn_gcn3_forward). */
 unsigned long long p2r_stgcn_gcn3h_signature(int form);
 int p2r_stgcn_gcn3h_pairs(int form, int *pairs);
 int p2r_stgcn_gcn3h_forward(int N, int T, int V, int K, int ltot, const float *x, const void *Wh, const float *winv,
@@ -795,7 +806,10 @@ int p2r_stgcn_gcn3h_data_gradient(int N, int T, int V, int K, int ltot, const fl
  * [n_blocks][64][53] (column sums of dz: the bias-table gradient), both summed over the leading axis by the caller -- with
  * K = 32 = (frame of a 4-frame tile) x (8 joints of a group) per MFMA.  coef [ltot][53]: the row-form coefficient table.
  * T % 4 == 0, x / dz 16-byte aligned; x_amax / dz_amax: range words of the two operand tensors (NULL: scale 1).
- * p2r_stgcn_gcn3h_weight_grad_signature() = signature of the row-form neighbour tables the schedule was generated for. */
+ * p2r_stgcn_gcn3h_weight_grad_signature() = signature of the row-form neighbour tables the schedule was generated for.
+ * Refused with P2R_EINVAL, nothing written: V != 53, K != 11, ltot != 62, T % 4 != 0, 64 T 53 floats of a sample beyond
+ * 2^31 bytes, x or dz misaligned or NULL, coef or dw_partial NULL, n_blocks outside 1 .. 65535.  A workgroup without a
+ * tile writes zeros; N == 0: every row of dw_partial and dbias_partial is zero (as p2r_stgcn_gcn3_weight_grad). */
 unsigned long long p2r_stgcn_gcn3h_weight_grad_signature(void);
 int p2r_stgcn_gcn3h_weight_grad(int N, int T, int V, int K, int ltot, const float *x, const float *dz, const float *coef,
                                 int n_blocks, float *dw_partial, float *dbias_partial, const unsigned *x_amax,
@@ -806,7 +820,11 @@ int p2r_stgcn_gcn3h_weight_grad(int N, int T, int V, int K, int ltot, const floa
  * rows of dz stays fp32 vector arithmetic (dz needs no range word).
  *   Wd    fp16 [K][4 ph][2 parts][2 ks][64 lanes][8]: the parts (w1, w2) of 2^S_w W_k (forward planes) in A-operand order,
  *         Wd[k][ph][part][ks][16 kg + r][i] = part of 2^S_w W_k[16 ph + r][32 ks + 16 (i >> 2) + 4 (i & 3) + kg]
- *   winv  device float 2^-S_w;  x_amax: range word of x (NULL: scale 1).  T % 16 == 0; x, dz, Wd 16-byte aligned. */
+ *   winv  device float 2^-S_w;  x_amax: range word of x (NULL: scale 1).  T % 16 == 0; x, dz, Wd 16-byte aligned.
+ * Refused with P2R_EINVAL, nothing written: V != 53, K != 11, ltot <= 0, T % 16 != 0, T > 2^19, x / dz / Wd misaligned, Wd
+ * or winv NULL, n_blocks outside 1 .. 65535.  ltot must be the row tables' 62 (as for p2r_stgcn_gcn3_coef_grad it sizes
+ * the table and is not checked against the schedule).  Padded slots come out exactly 0.  N == 0: dcoef_partial is
+ * zero-filled (as p2r_stgcn_gcn3_coef_grad). */
 int p2r_stgcn_gcn3h_coef_grad(int N, int T, int V, int K, int ltot, const float *x, const float *dz, const void *Wd,
                               const float *winv, int n_blocks, float *dcoef_partial, const unsigned *x_amax,
                               void *stream);

@@ -91,6 +91,7 @@ extern "C" int p2r_stgcn_gcn3h_coef_grad(int N, int T, int V, int K, int ltot, c
                                          const void *Wd, const float *winv, int n_blocks, float *dcoef_partial,
                                          const unsigned *x_amax, void *stream) {
   if (!Wd || !winv || T > (1 << 19) || ((uintptr_t)x % 16) != 0 || ((uintptr_t)Wd % 16) != 0) return P2R_EINVAL;
+  if (n_blocks > 65535) return P2R_EINVAL;                    // as p2r_stgcn_gcn3h_weight_grad: one partial row per workgroup
   return d3_launch(N, T, V, K, ltot, x, dz, reinterpret_cast<const p2r_h8 *>(Wd), n_blocks, dcoef_partial, stream,
                    D3Extra{x_amax, winv});
 }

@@ -231,7 +231,7 @@ extern "C" int p2r_stgcn_tconvh_forward(int N, int T, int V, const float *x, con
                                         const unsigned *x_amax, void *stream) {
   if (N < 0 || T <= 0 || V != TH_V || (scale == nullptr) != (shift == nullptr)) return P2R_EINVAL;
   if ((bwd_z == nullptr) != (bwd_fin == nullptr) || (bwd_z && (scale || !stats_partial))) return P2R_EINVAL;
-  if (T % 16 != 0 || T > (1 << 20)) return P2R_EINVAL;
+  if (T % 16 != 0 || T > (1 << 20) || ((uintptr_t)Wh % 16) != 0) return P2R_EINVAL;     // (refused before *n_partials is written)
   if (n_partials) *n_partials = 0;
   if (N == 0) return P2R_OK;
   const int FC = tconvh_chunk(T);
@@ -239,7 +239,7 @@ extern "C" int p2r_stgcn_tconvh_forward(int N, int T, int V, const float *x, con
   if (blocks > 0x7fffffffLL) return P2R_EINVAL;
   if (n_partials) *n_partials = (int)blocks;
   if (!out) return P2R_OK;
-  if (!Wh || !winv || ((uintptr_t)Wh % 16) != 0) return P2R_EINVAL;
+  if (!Wh || !winv) return P2R_EINVAL;
   const p2r_h8 *wh = reinterpret_cast<const p2r_h8 *>(Wh);
   hipStream_t st = p2r_stream(stream);
 #define P2R_TH(XF, BW) hipLaunchKernelGGL((tconvh_kernel<XF, BW>), dim3((unsigned)blocks), dim3(256), 0, st, T, FC, x, scale, \
