@@ -261,6 +261,15 @@ class SceneBatch(object):
         from . import occupancy_device
         return occupancy_device.occupancy_of(self, grid, joints=joints, gt=gt, min_votes=min_votes, owner=owner)
 
+    def interactions(self, joints, contact_thresh=None, merge_gap=0, min_len=1, max_intervals=16, labels=True):
+        """-> interaction_device.InteractionBatch: per node the frames of joints (B,T,J,3|4) in which the body is inside
+        the node's box enlarged by contact_thresh (default: the distance the training labels use), as bit-packed frames
+        and as intervals merged over gaps of at most merge_gap frames and at least min_len long, the joints that touch
+        it, and with labels one node per frame.  Three launches (two without labels), nothing crosses to the host."""
+        from . import interaction_device
+        return interaction_device.interactions_of(self, joints, contact_thresh=contact_thresh, merge_gap=merge_gap,
+                                                  min_len=min_len, max_intervals=max_intervals, labels=labels)
+
     def save_npz(self, path, n):
         """Sample n in the layout of the reference's `%06d_pred_confident_nms_bbox.npz` (testing.py:132-134: obbs, cls,
         inst_idx), which its `read_pred` reads.  -> True, or False for a sample without nodes: the reference writes no

@@ -237,6 +237,18 @@ class P2RNet(BaseNetwork):
         return scenes.occupancy(grid, joints=data['input_joints'] if body else None, gt=gt, min_votes=min_votes,
                                 owner=owner)
 
+    def predict_interactions(self, data, num_hypotheses=None, n_samples=None, seed=None, dump_threshold=None,
+                             contact_thresh=None, merge_gap=0, min_len=1, max_intervals=16):
+        """When the body is in contact with which predicted object: `predict_scenes(...)` with the same arguments, then
+        `SceneBatch.interactions(data['input_joints'], ...)` -- per node the contact frames as intervals, merged over
+        gaps of at most `merge_gap` frames and at least `min_len` long, the joints that touch it, and per frame the node
+        the body is most in contact with (net_utils.interaction_device.InteractionBatch; its `.scenes` is the
+        SceneBatch).  Nothing more crosses to the host than in `predict_scenes`."""
+        scenes = self.predict_scenes(data, num_hypotheses=num_hypotheses, n_samples=n_samples, seed=seed,
+                                     dump_threshold=dump_threshold, contact=True, unique=False)
+        return scenes.interactions(data['input_joints'], contact_thresh=contact_thresh, merge_gap=merge_gap,
+                                   min_len=min_len, max_intervals=max_intervals)
+
     def loss(self, pred_data, gt_data):
         if isinstance(pred_data, tuple):
             pred_data = pred_data[0]
