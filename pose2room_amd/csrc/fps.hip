@@ -394,8 +394,8 @@ extern "C" int p2r_furthest_point_sampling(int b, int n, int m, const float *dat
   if (G >= 2 && S <= 16384 && (reinterpret_cast<uintptr_t>(temp) & 7) == 0 &&
       (size_t)b * 4 * G * sizeof(unsigned long long) <= (size_t)b * n * sizeof(float)) {
     int rc;
-    if (S <= 1024) rc = launch_coop<1>(b, G, S, n, m, L, dataset, temp, idxs, st);
-    else if (S <= 2048) rc = launch_coop<2>(b, G, S, n, m, L, dataset, temp, idxs, st);
+    // S >= 1025 here (n > 16384 over G <= 16 workgroups): a one-point-per-lane tiling cannot be reached and is not built
+    if (S <= 2048) rc = launch_coop<2>(b, G, S, n, m, L, dataset, temp, idxs, st);
     else if (S <= 4096) rc = launch_coop<4>(b, G, S, n, m, L, dataset, temp, idxs, st);
     else if (S <= 8192) rc = launch_coop<8>(b, G, S, n, m, L, dataset, temp, idxs, st);
     else rc = launch_coop<16>(b, G, S, n, m, L, dataset, temp, idxs, st);
