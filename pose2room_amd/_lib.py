@@ -1,15 +1,18 @@
-"""ctypes loader for libp2r_hip.so (C ABI declared in include/p2r_hip.h).
+"""ctypes loader for libp2r_hip.so (C ABI declared in include/p2r_hip.h) and for the extension libraries next to it.
 
-The library is built in-tree by `pose2room_amd/csrc/Makefile`
+The libraries are built in-tree by `pose2room_amd/csrc/Makefile`
 (`__graft_entry__.build()`).  Loading fails loudly: there is no Python or CPU
 fallback for any entry point.
 
-The header is the one declaration of the ABI: `prototypes()` parses it into the `argtypes` / `restype` of every entry
-point, `struct()` into the `ctypes.Structure` of every `typedef struct`, and `launch` / `launch_on` check a call
-against its prototype before anything is enqueued.  The parser is no C parser.  It reads the subset the header uses
--- `/* */` comments, preprocessor lines, `typedef struct { ... } name;` blocks of pointer / int / long long / double
-fields, and prototypes `type p2r_name(type name, ...);` over int, float, double, long long, unsigned long long and
-pointers -- and raises P2RLibraryError, naming the declaration, on anything else.
+A header is the one declaration of its library's ABI, and a `Library` binds the two: `prototypes()` parses the header
+into the `argtypes` / `restype` of every entry point, `struct()` into the `ctypes.Structure` of every `typedef struct`,
+and `launch` / `launch_on` check a call against its prototype before anything is enqueued.  `main` is libp2r_hip.so;
+the module-level `lib`, `marshal`, `launch_on` and `launch` are its methods.
+
+The parser is no C parser.  It reads the subset the headers use -- `/* */` comments, preprocessor lines,
+`typedef struct { ... } name;` blocks of pointer / int / long long / double fields, and prototypes
+`type p2r_name(type name, ...);` over int, float, double, long long, unsigned long long and pointers -- and raises
+P2RLibraryError, naming the header and the declaration, on anything else.
 """
 import collections
 import ctypes
@@ -25,8 +28,6 @@ LIB_PATH = os.environ.get("P2R_LIB_PATH") or os.path.join(_HERE, "libp2r_hip.so"
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "p2r_hip.h")
 
 ABI_VERSION = 3     # p2r_abi_version() of the library this loader was written against (include/p2r_hip.h)
-
-_lib = None
 
 
 class P2RLibraryError(RuntimeError):
@@ -64,7 +65,7 @@ def _ctype(decl, what):
         return ctypes.c_void_p
     base = " ".join(t for t in decl.split() if t != "const")
     if base not in _SCALARS:
-        raise P2RLibraryError(f"include/p2r_hip.h: type '{base}' in `{what}` is outside the subset the binding maps "
+        raise P2RLibraryError(f"type '{base}' in `{what}` is outside the subset the binding maps "
                               f"({', '.join(_SCALARS)}, pointers)")
     return _SCALARS[base]
 
@@ -75,7 +76,7 @@ def _parse_prototype(ret, name, params):
     if ret == "const char *":
         restype = ctypes.c_char_p
     elif "*" in ret:
-        raise P2RLibraryError(f"include/p2r_hip.h: return type '{ret}' of `{text}` is outside the subset the binding maps")
+        raise P2RLibraryError(f"return type '{ret}' of `{text}` is outside the subset the binding maps")
     else:
         restype = _ctype(ret, text)
     argtypes, names = [], []
@@ -83,7 +84,7 @@ def _parse_prototype(ret, name, params):
         for p in params.split(","):
             m = re.fullmatch(r"\s*(.*?[\s\*])(\w+)\s*", p, flags=re.S)
             if m is None:
-                raise P2RLibraryError(f"include/p2r_hip.h: cannot read parameter '{p.strip()}' of `{text}`")
+                raise P2RLibraryError(f"cannot read parameter '{p.strip()}' of `{text}`")
             argtypes.append(_ctype(m.group(1), text))
             names.append(m.group(2))
     has_stream = bool(names) and names[-1] in ("stream", "stream_h") and argtypes[-1] is ctypes.c_void_p
@@ -100,13 +101,13 @@ def _parse_struct(body, name):
         first, *more = decl.split(",")
         m = re.fullmatch(r"\s*(.*?[\s\*])(\w+)\s*", first, flags=re.S)
         if m is None:
-            raise P2RLibraryError(f"include/p2r_hip.h: cannot read field '{decl.strip()}' of struct {name}")
+            raise P2RLibraryError(f"cannot read field '{decl.strip()}' of struct {name}")
         base = m.group(1).replace("*", " ")
         pieces = [(m.group(1), m.group(2))]
         for d in more:       # further declarators of the line share the base type: `const float *x, *x2;`
             m = re.fullmatch(r"\s*(\**)\s*(\w+)\s*", d)
             if m is None:
-                raise P2RLibraryError(f"include/p2r_hip.h: cannot read field '{decl.strip()}' of struct {name}")
+                raise P2RLibraryError(f"cannot read field '{decl.strip()}' of struct {name}")
             pieces.append((base + m.group(1), m.group(2)))
         for typ, field in pieces:
             fields.append((field + "_" if keyword.iskeyword(field) else field, _ctype(typ, f"struct {name}: {decl.strip()}")))
@@ -114,56 +115,17 @@ def _parse_struct(body, name):
 
 
 def _parse(header_path):
+    """-> ({name: Prototype}, {name: ctypes.Structure}) of the header; an error names the header it was reading"""
     code = _code(header_path)
-    structs = {m.group(2): _parse_struct(m.group(1), m.group(2)) for m in _STRUCT_RE.finditer(code)}
-    protos = {m.group(2): _parse_prototype(*m.groups()) for m in _PROTO_RE.finditer(_STRUCT_RE.sub("", code))}
-    unread = sorted(set(declared_symbols(header_path)) - set(protos))
-    if unread:
-        raise P2RLibraryError(f"include/p2r_hip.h: the declarations of {unread} are outside the subset the binding reads")
+    try:
+        structs = {m.group(2): _parse_struct(m.group(1), m.group(2)) for m in _STRUCT_RE.finditer(code)}
+        protos = {m.group(2): _parse_prototype(*m.groups()) for m in _PROTO_RE.finditer(_STRUCT_RE.sub("", code))}
+        unread = sorted(set(declared_symbols(header_path)) - set(protos))
+        if unread:
+            raise P2RLibraryError(f"the declarations of {unread} are outside the subset the binding reads")
+    except P2RLibraryError as e:
+        raise P2RLibraryError(f"{os.path.basename(header_path)}: {e}") from None
     return protos, structs
-
-
-_parsed = None
-
-
-def _header():
-    global _parsed
-    if _parsed is None:
-        _parsed = _parse(HEADER_PATH)
-    return _parsed
-
-
-def prototypes(header_path=None):
-    """name -> Prototype of every entry point the header declares."""
-    return _header()[0] if header_path is None else _parse(header_path)[0]
-
-
-def struct(name, header_path=None):
-    """The ctypes.Structure of the header's `typedef struct { ... } name;` (a field named like a Python keyword gets a
-    trailing underscore: p2r_pw_rjob.in is `in_`).  header_path: an extension library's header instead."""
-    return _header()[1][name] if header_path is None else _parse(header_path)[1][name]
-
-
-def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise P2RLibraryError(
-                f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(or `make -C pose2room_amd/csrc`). pose2room_amd has no CPU fallback.")
-        try:
-            l = ctypes.CDLL(LIB_PATH)
-        except OSError as e:  # pragma: no cover
-            raise P2RLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-        l.p2r_abi_version.restype = ctypes.c_int
-        if l.p2r_abi_version() != ABI_VERSION:
-            raise P2RLibraryError(f"libp2r_hip.so ABI version {l.p2r_abi_version()} != {ABI_VERSION}: stale library, rebuild it "
-                                  "(make -C pose2room_amd/csrc)")
-        for name, proto in prototypes().items():
-            fn = getattr(l, name)
-            fn.restype, fn.argtypes = proto.restype, proto.argtypes
-        _lib = l
-    return _lib
 
 
 def check(status, what):
@@ -204,44 +166,109 @@ def _scalar(proto, i, a):
     return float(a)
 
 
-def marshal(name, args):
-    """`args` = the parameters of entry point `name` in header order, without the trailing stream -> the list that goes
-    to the library: tensors as their address, None as NULL, integers as Python ints.  Raises TypeError unless the count
-    is exact (ctypes accepts surplus arguments) and every argument is of its parameter's kind.  Needs no GPU."""
-    proto = _header()[0].get(name)
-    if proto is None:
-        raise P2RLibraryError(f"{name} is not declared in include/p2r_hip.h")
-    if len(args) != len(proto.pointer):
-        raise TypeError(f"{name}: {len(args)} arguments for {len(proto.pointer)} parameters"
-                        f"{' in front of the stream' if proto.has_stream else ''}: {proto.text}")
-    try:        # the common case in one pass: every pointer a tensor or None
-        out = [a.data_ptr() if p and a is not None else a for a, p in zip(args, proto.pointer)]
-    except AttributeError:      # host arrays (job lists, counts), byref(struct), plain addresses
-        out = [_address(proto, i, a) if p and a is not None else a for i, (a, p) in enumerate(zip(args, proto.pointer))]
-    for i in proto.scalars:
-        if type(out[i]) is not int:
-            out[i] = _scalar(proto, i, out[i])
-    return out
+class Library(object):
+    """One shared library bound from its header: libp2r_hip.so (`main` below) and every extension library next to it
+    (csrc/Makefile: EXTS) is one of these.  The header is read once per object, at the first use; the library is loaded
+    by the first `lib()`.  abi_version: what the library's p2r_abi_version() must return, where it has one."""
+
+    def __init__(self, header_path, lib_path, abi_version=None):
+        self.header_path, self.lib_path, self.abi_version = header_path, lib_path, abi_version
+        self._protos = self._structs = self._handle = None
+
+    def prototypes(self):
+        """name -> Prototype of every entry point the header declares."""
+        if self._protos is None:
+            self._protos, self._structs = _parse(self.header_path)
+        return self._protos
+
+    def struct(self, name):
+        """The ctypes.Structure of the header's `typedef struct { ... } name;` (a field named like a Python keyword gets
+        a trailing underscore: p2r_pw_rjob.in is `in_`)."""
+        self.prototypes()
+        return self._structs[name]
+
+    def lib(self):
+        """The ctypes.CDLL with the header's restype / argtypes on every entry point.  A missing library is an error."""
+        if self._handle is None:
+            if not os.path.exists(self.lib_path):
+                raise P2RLibraryError(
+                    f"{self.lib_path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                    "(or `make -C pose2room_amd/csrc`). pose2room_amd has no CPU fallback.")
+            try:
+                l = ctypes.CDLL(self.lib_path)
+            except OSError as e:  # pragma: no cover
+                raise P2RLibraryError(f"cannot load {self.lib_path}: {e}") from e
+            if self.abi_version is not None:
+                l.p2r_abi_version.restype = ctypes.c_int
+                if l.p2r_abi_version() != self.abi_version:
+                    raise P2RLibraryError(f"{os.path.basename(self.lib_path)} ABI version {l.p2r_abi_version()} != "
+                                          f"{self.abi_version}: stale library, rebuild it (make -C pose2room_amd/csrc)")
+            for name, proto in self.prototypes().items():
+                fn = getattr(l, name)
+                fn.restype, fn.argtypes = proto.restype, proto.argtypes
+            self._handle = l
+        return self._handle
+
+    # The three below run thousands of times per train step: `self._protos or ...` and `self._handle or ...` are the
+    # loaded state read without a call.
+    def marshal(self, name, args):
+        """`args` = the parameters of entry point `name` in header order, without the trailing stream -> the list that
+        goes to the library: tensors as their address, None as NULL, integers as Python ints.  Raises TypeError unless
+        the count is exact (ctypes accepts surplus arguments) and every argument is of its parameter's kind.  Needs no
+        GPU."""
+        proto = (self._protos or self.prototypes()).get(name)
+        if proto is None:
+            raise P2RLibraryError(f"{name} is not declared in {os.path.basename(self.header_path)}")
+        if len(args) != len(proto.pointer):
+            raise TypeError(f"{name}: {len(args)} arguments for {len(proto.pointer)} parameters"
+                            f"{' in front of the stream' if proto.has_stream else ''}: {proto.text}")
+        try:        # the common case in one pass: every pointer a tensor or None
+            out = [a.data_ptr() if p and a is not None else a for a, p in zip(args, proto.pointer)]
+        except AttributeError:      # host arrays (job lists, counts), byref(struct), plain addresses
+            out = [_address(proto, i, a) if p and a is not None else a
+                   for i, (a, p) in enumerate(zip(args, proto.pointer))]
+        for i in proto.scalars:
+            if type(out[i]) is not int:
+                out[i] = _scalar(proto, i, out[i])
+        return out
+
+    def launch_on(self, name, stream, *args):
+        """Entry point `name` on `stream` (what `current_stream` returns), for a block of launches under one device
+        guard and one stream lookup, both the caller's.  The entry point is looked up at every call: bench.py and the
+        tests replace attributes of the library object to time or trap launches."""
+        if not (self._protos or self.prototypes())[name].has_stream:
+            raise TypeError(f"{name} takes no stream: call lib().{name} directly")
+        check(getattr(self._handle or self.lib(), name)(*self.marshal(name, args), stream), name)
+
+    def launch(self, name, device, *args):
+        """One launch of entry point `name` on the current stream of `device`, made current for the call; `args` as
+        for `marshal`.  Raises when the library returns a non-zero status."""
+        import torch
+        if device.index is None or device.index == torch.cuda.current_device():
+            self.launch_on(name, current_stream(device), *args)     # `device` is current: a guard would change nothing
+        else:
+            with torch.cuda.device(device):
+                self.launch_on(name, current_stream(device), *args)
 
 
-def launch_on(name, stream, *args):
-    """Entry point `name` on `stream` (what `current_stream` returns), for a block of launches under one device guard
-    and one stream lookup, both the caller's.  The entry point is looked up at every call: bench.py and the tests
-    replace attributes of the library object to time or trap launches."""
-    if not _header()[0][name].has_stream:
-        raise TypeError(f"{name} takes no stream: call lib().{name} directly")
-    check(getattr(lib(), name)(*marshal(name, args), stream), name)
+def extension(name):
+    """The Library of extension `name`: libp2r_<name>.so next to libp2r_hip.so, bound from include/p2r_<name>.h."""
+    return Library(os.path.join(os.path.dirname(HEADER_PATH), f"p2r_{name}.h"), os.path.join(_HERE, f"libp2r_{name}.so"))
 
 
-def launch(name, device, *args):
-    """One launch of entry point `name` on the current stream of `device`, made current for the call; `args` as for
-    `marshal`.  Raises when the library returns a non-zero status."""
-    import torch
-    if device.index is None or device.index == torch.cuda.current_device():
-        launch_on(name, current_stream(device), *args)      # `device` is current already: a guard would change nothing
-    else:
-        with torch.cuda.device(device):
-            launch_on(name, current_stream(device), *args)
+# libp2r_hip.so itself, and its methods under the names the ops, bench.py, the tests and tools/ call
+main = Library(HEADER_PATH, LIB_PATH, ABI_VERSION)
+lib, marshal, launch_on, launch = main.lib, main.marshal, main.launch_on, main.launch
+
+
+def prototypes(header_path=None):
+    """name -> Prototype of every entry point of p2r_hip.h; with header_path, of that header, read at every call."""
+    return main.prototypes() if header_path is None else _parse(header_path)[0]
+
+
+def struct(name, header_path=None):
+    """`Library.struct` of p2r_hip.h; with header_path, of that header, read at every call."""
+    return main.struct(name) if header_path is None else _parse(header_path)[1][name]
 
 
 def sum_leading(part, tr64=False):

@@ -18,9 +18,6 @@ the device tensors `parse_predictions(..., return_device=True)` returns:
 Equal scores: within one (scan, class) the lower proposal index goes first; across scans the earlier scan.  The
 reference's `np.argsort(-score)` is not stable and defines no order there.  No CPU fallback.
 """
-import ctypes
-import os
-
 import numpy as np
 import torch
 
@@ -32,34 +29,10 @@ NOT_A_DETECTION = 255      # flag byte of a (proposal, class) slot that holds no
 MAX_K, MAX_G, MAX_C, MAX_T = 1024, 256, 64, 8      # limits of the entry points (include/p2r_ap_eval.h)
 
 # The two kernels are a library of their own next to libp2r_hip.so (csrc/Makefile), with a header of their own; the
-# binding is derived from that header by the parser that binds libp2r_hip.so (_lib.prototypes).
-HEADER_PATH = os.path.join(os.path.dirname(_lib.HEADER_PATH), "p2r_ap_eval.h")
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(_lib.__file__)), "libp2r_ap_eval.so")
-_ap_lib = None
-
-
-def lib():
-    """libp2r_ap_eval.so with the argtypes of include/p2r_ap_eval.h; a missing library is an error (no fallback)."""
-    global _ap_lib
-    if _ap_lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise _lib.P2RLibraryError(f"{LIB_PATH} is missing: build it with `make -C pose2room_amd/csrc` "
-                                       "(pose2room_amd has no CPU fallback)")
-        l = ctypes.CDLL(LIB_PATH)
-        for name, proto in _lib.prototypes(HEADER_PATH).items():
-            fn = getattr(l, name)
-            fn.restype, fn.argtypes = proto.restype, proto.argtypes
-        _ap_lib = l
-    return _ap_lib
-
-
-def _launch(name, device, *args):
-    """entry point `name` on the current stream of `device`: tensors as their address, None as NULL"""
-    fn = getattr(lib(), name)
-    if len(args) + 1 != len(fn.argtypes):
-        raise TypeError(f"{name}: {len(args)} arguments for {len(fn.argtypes) - 1} parameters in front of the stream")
-    with torch.cuda.device(device):
-        _lib.check(fn(*[a.data_ptr() if torch.is_tensor(a) else a for a in args], _lib.current_stream(device)), name)
+# binding is derived from that header as that of libp2r_hip.so is (_lib.Library).
+_library = _lib.extension("ap_eval")
+HEADER_PATH, LIB_PATH = _library.header_path, _library.lib_path
+lib, _launch = _library.lib, _library.launch
 
 
 def _need_cuda(what, **tensors):

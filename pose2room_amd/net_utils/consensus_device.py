@@ -25,8 +25,6 @@ Mean size and mean heading are deliberately absent: boxes at theta and theta + p
 sizes, are the same solid, so an average of those parameters is not defined.  The leader's box is the representative.
 """
 import collections
-import ctypes
-import os
 
 import numpy as np
 import torch
@@ -37,29 +35,14 @@ from .scene_device import _on_gpu, _want
 
 MAX_H, MAX_K, MAX_POOL = 64, 1024, 2048        # P2R_CONSENSUS_MAX_H / _K / _POOL of include/p2r_consensus.h
 
-HEADER_PATH = os.path.join(os.path.dirname(_lib.HEADER_PATH), "p2r_consensus.h")
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(_lib.__file__)), "libp2r_consensus.so")
-_consensus_lib = None
+_library = _lib.extension("consensus")
+HEADER_PATH, LIB_PATH = _library.header_path, _library.lib_path
+lib = _library.lib
 
 # capacity Mc = H * K per sample; unused slots are zero, -1 for leader_node; cluster_of is (N,K), -1 from count on
 Consensus = collections.namedtuple(
     'Consensus', 'n_clusters leader_node members support hyp_mask box cls score score_mean center_mean center_rms '
                  'iou_mean cluster_of')
-
-
-def lib():
-    """libp2r_consensus.so with the argtypes of include/p2r_consensus.h; a missing library is an error (no fallback)."""
-    global _consensus_lib
-    if _consensus_lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise _lib.P2RLibraryError(f"{LIB_PATH} is missing: build it with `make -C pose2room_amd/csrc` "
-                                       "(pose2room_amd has no CPU fallback)")
-        l = ctypes.CDLL(LIB_PATH)
-        for name, proto in _lib.prototypes(HEADER_PATH).items():
-            fn = getattr(l, name)
-            fn.restype, fn.argtypes = proto.restype, proto.argtypes
-        _consensus_lib = l
-    return _consensus_lib
 
 
 def _output_specs(H, B, K):
@@ -95,17 +78,13 @@ def consensus_clusters(count, node_obbs, node_cls, node_score, H, iou_thresh=0.2
     count, node_obbs, node_cls, node_score = _on_gpu(what, count=count, node_obbs=node_obbs, node_cls=node_cls,
                                                      node_score=node_score)
     dev, B = count.device, N // H
-    l = lib()
-    need = int(l.p2r_consensus_workspace_bytes(H, B, K))
+    need = int(lib().p2r_consensus_workspace_bytes(H, B, K))
     out = [torch.empty(shape, dtype=dtype, device=dev) for _, shape, dtype in _output_specs(H, B, K)]
     workspace = torch.empty((need // 8,), dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(l.p2r_consensus(H, B, K, count.data_ptr(), node_obbs.data_ptr(), node_cls.data_ptr(),
-                                   node_score.data_ptr(), iou_thresh, int(bool(class_aware)),
-                                   *[t.data_ptr() for t in out], workspace.data_ptr(), need,
-                                   _lib.current_stream(dev)), "p2r_consensus")
-        # the workspace goes back to the caching allocator here; the allocator hands it out again only to work enqueued
-        # on this stream, behind the two launches
+    _library.launch("p2r_consensus", dev, H, B, K, count, node_obbs, node_cls, node_score, iou_thresh,
+                    int(bool(class_aware)), *out, workspace, need)
+    # the workspace goes back to the caching allocator here; the allocator hands it out again only to work enqueued on
+    # this stream, behind the two launches
     return Consensus(*out)
 
 

@@ -29,8 +29,6 @@ Sample n of an N = H * B stack reads joints row n % B.  Slot s of sample n is a 
              -1 without one.
 """
 import collections
-import ctypes
-import os
 
 import numpy as np
 import torch
@@ -42,33 +40,9 @@ from .scene_device import _on_gpu, _want, _want_joints
 MAX_K, MAX_T, MAX_J, MAX_M = 1024, 65535, 64, 64           # P2R_INTERACTION_MAX_K / _T / _J / _M of the header
 MAX_ELEMS = 0x7fffffff
 
-HEADER_PATH = os.path.join(os.path.dirname(_lib.HEADER_PATH), "p2r_interaction.h")
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(_lib.__file__)), "libp2r_interaction.so")
-_interaction_lib = None
-
-
-def lib():
-    """libp2r_interaction.so with the argtypes of include/p2r_interaction.h; a missing library is an error (no fallback)."""
-    global _interaction_lib
-    if _interaction_lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise _lib.P2RLibraryError(f"{LIB_PATH} is missing: build it with `make -C pose2room_amd/csrc` "
-                                       "(pose2room_amd has no CPU fallback)")
-        l = ctypes.CDLL(LIB_PATH)
-        for name, proto in _lib.prototypes(HEADER_PATH).items():
-            fn = getattr(l, name)
-            fn.restype, fn.argtypes = proto.restype, proto.argtypes
-        _interaction_lib = l
-    return _interaction_lib
-
-
-def _launch(name, device, *args):
-    """entry point `name` on the current stream of `device`: tensors as their address, None as NULL"""
-    fn = getattr(lib(), name)
-    if len(args) + 1 != len(fn.argtypes):
-        raise TypeError(f"{name}: {len(args)} arguments for {len(fn.argtypes) - 1} parameters in front of the stream")
-    with torch.cuda.device(device):
-        _lib.check(fn(*[a.data_ptr() if torch.is_tensor(a) else a for a in args], _lib.current_stream(device)), name)
+_library = _lib.extension("interaction")
+HEADER_PATH, LIB_PATH = _library.header_path, _library.lib_path
+lib, _launch = _library.lib, _library.launch
 
 
 def words_of(T):

@@ -18,9 +18,6 @@ evaluates its runs: H x T host `APCalculator`s, every hypothesis' predictions co
 
 No CPU fallback.
 """
-import ctypes
-import os
-
 import numpy as np
 import torch
 
@@ -31,34 +28,10 @@ from .ap_device import DeviceAPCalculator, _need_cuda
 MAX_H, MAX_K = 64, 1024        # limits of p2r_tmd (include/p2r_mm_eval.h)
 
 # The two kernels are a third library next to libp2r_hip.so and libp2r_ap_eval.so (csrc/Makefile), with a header of
-# their own; the binding is derived from that header by the parser that binds libp2r_hip.so (_lib.prototypes).
-HEADER_PATH = os.path.join(os.path.dirname(_lib.HEADER_PATH), "p2r_mm_eval.h")
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(_lib.__file__)), "libp2r_mm_eval.so")
-_mm_lib = None
-
-
-def lib():
-    """libp2r_mm_eval.so with the argtypes of include/p2r_mm_eval.h; a missing library is an error (no fallback)."""
-    global _mm_lib
-    if _mm_lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise _lib.P2RLibraryError(f"{LIB_PATH} is missing: build it with `make -C pose2room_amd/csrc` "
-                                       "(pose2room_amd has no CPU fallback)")
-        l = ctypes.CDLL(LIB_PATH)
-        for name, proto in _lib.prototypes(HEADER_PATH).items():
-            fn = getattr(l, name)
-            fn.restype, fn.argtypes = proto.restype, proto.argtypes
-        _mm_lib = l
-    return _mm_lib
-
-
-def _launch(name, device, *args):
-    """entry point `name` on the current stream of `device`: tensors as their address"""
-    fn = getattr(lib(), name)
-    if len(args) + 1 != len(fn.argtypes):
-        raise TypeError(f"{name}: {len(args)} arguments for {len(fn.argtypes) - 1} parameters in front of the stream")
-    with torch.cuda.device(device):
-        _lib.check(fn(*[a.data_ptr() if torch.is_tensor(a) else a for a in args], _lib.current_stream(device)), name)
+# their own; the binding is derived from that header as that of libp2r_hip.so is (_lib.Library).
+_library = _lib.extension("mm_eval")
+HEADER_PATH, LIB_PATH = _library.header_path, _library.lib_path
+lib, _launch = _library.lib, _library.launch
 
 
 def box_params(corners):

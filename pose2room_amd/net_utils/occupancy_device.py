@@ -32,9 +32,7 @@ origin[a] + ((double)index_a + 0.5) * voxel per axis.  Dense arrays are (.., nz,
   counts  per sample n with rows n % B of the ground-truth and body maps: vol, vol_gt, inter_gt, vol_body, inter_body.
 """
 import collections
-import ctypes
 import math
-import os
 
 import numpy as np
 import torch
@@ -46,35 +44,11 @@ MAX_DIM, MAX_K, MAX_H, NODE_CHUNK = 1024, 1024, 64, 128    # P2R_OCC_MAX_DIM / _
 MAX_ELEMS = 0x7fffffff
 MAX_T = 65535                                              # scene_device.MAX_T: the recordings `contact_frames` takes
 
-HEADER_PATH = os.path.join(os.path.dirname(_lib.HEADER_PATH), "p2r_occupancy.h")
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(_lib.__file__)), "libp2r_occupancy.so")
-_occupancy_lib = None
+_library = _lib.extension("occupancy")
+HEADER_PATH, LIB_PATH = _library.header_path, _library.lib_path
+lib, _launch = _library.lib, _library.launch
 
 COUNT_FIELDS = ('vol', 'vol_gt', 'inter_gt', 'vol_body', 'inter_body')
-
-
-def lib():
-    """libp2r_occupancy.so with the argtypes of include/p2r_occupancy.h; a missing library is an error (no fallback)."""
-    global _occupancy_lib
-    if _occupancy_lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise _lib.P2RLibraryError(f"{LIB_PATH} is missing: build it with `make -C pose2room_amd/csrc` "
-                                       "(pose2room_amd has no CPU fallback)")
-        l = ctypes.CDLL(LIB_PATH)
-        for name, proto in _lib.prototypes(HEADER_PATH).items():
-            fn = getattr(l, name)
-            fn.restype, fn.argtypes = proto.restype, proto.argtypes
-        _occupancy_lib = l
-    return _occupancy_lib
-
-
-def _launch(name, device, *args):
-    """entry point `name` on the current stream of `device`: tensors as their address, None as NULL"""
-    fn = getattr(lib(), name)
-    if len(args) + 1 != len(fn.argtypes):
-        raise TypeError(f"{name}: {len(args)} arguments for {len(fn.argtypes) - 1} parameters in front of the stream")
-    with torch.cuda.device(device):
-        _lib.check(fn(*[a.data_ptr() if torch.is_tensor(a) else a for a in args], _lib.current_stream(device)), name)
 
 
 # ---- the grid ----------------------------------------------------------------------------------------------------------

@@ -11,9 +11,6 @@ H * B batch (`joints_repeat`), which then needs no H-fold copy of the joints.
 launch; `parse_predictions(..., impl='kernel')` and `test.parse_impl: 'kernel'` route through it.  The two paths differ
 by the device's `exp` / `atan2` / `cos` / `sin` against ATen's, nothing else.  No CPU fallback.
 """
-import ctypes
-import os
-
 import torch
 
 from .. import _lib
@@ -24,25 +21,10 @@ CHUNK_FRAMES = 256                         # frames the kernel stages per pass t
 GROUP_BOXES = 16                           # proposals per workgroup (PB)
 
 # The kernel is a library of its own next to libp2r_hip.so (csrc/Makefile), with a header of its own; the binding is
-# derived from that header by the parser that binds libp2r_hip.so (_lib.prototypes).
-HEADER_PATH = os.path.join(os.path.dirname(_lib.HEADER_PATH), "p2r_parse.h")
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(_lib.__file__)), "libp2r_parse.so")
-_parse_lib = None
-
-
-def lib():
-    """libp2r_parse.so with the argtypes of include/p2r_parse.h; a missing library is an error (no fallback)."""
-    global _parse_lib
-    if _parse_lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise _lib.P2RLibraryError(f"{LIB_PATH} is missing: build it with `make -C pose2room_amd/csrc` "
-                                       "(pose2room_amd has no CPU fallback)")
-        l = ctypes.CDLL(LIB_PATH)
-        for name, proto in _lib.prototypes(HEADER_PATH).items():
-            fn = getattr(l, name)
-            fn.restype, fn.argtypes = proto.restype, proto.argtypes
-        _parse_lib = l
-    return _parse_lib
+# derived from that header as that of libp2r_hip.so is (_lib.Library).
+_library = _lib.extension("parse")
+HEADER_PATH, LIB_PATH = _library.header_path, _library.lib_path
+lib = _library.lib
 
 
 def _want(what, name, t, dtype, shape):
@@ -102,14 +84,9 @@ def parse_boxes(center, size_log, heading_sc, objectness, sem_scores, joints=Non
     obj_prob = torch.empty((N, K), dtype=torch.float32, device=dev)
     pred_cls = torch.empty((N, K), dtype=torch.int64, device=dev)
     nonempty = torch.empty((N, K), dtype=torch.uint8, device=dev)
-    args = (center, size_log, heading_sc, objectness, sem_scores, cls_in, joints, N, K, C, Bj, T, J, int(origin_joint),
-            float(contact_dist), int(bool(remove_far_box)), int(nms_mode), corners, boxes, obj_prob, pred_cls, nonempty)
-    fn = lib().p2r_parse_boxes
-    if len(args) + 1 != len(fn.argtypes):
-        raise TypeError(f"p2r_parse_boxes: {len(args)} arguments for {len(fn.argtypes) - 1} parameters in front of the stream")
-    with torch.cuda.device(dev):
-        _lib.check(fn(*[a.data_ptr() if torch.is_tensor(a) else a for a in args], _lib.current_stream(dev)),
-                   "p2r_parse_boxes")
+    _library.launch("p2r_parse_boxes", dev, center, size_log, heading_sc, objectness, sem_scores, cls_in, joints, N, K, C,
+                    Bj, T, J, int(origin_joint), float(contact_dist), int(bool(remove_far_box)), int(nms_mode), corners,
+                    boxes, obj_prob, pred_cls, nonempty)
     return corners, boxes, obj_prob, pred_cls, nonempty
 
 

@@ -20,7 +20,6 @@ No CPU fallback: the mirror is what the tests compare against, not a second impl
 """
 import collections
 import ctypes
-import os
 
 import numpy as np
 import torch
@@ -33,9 +32,9 @@ MEASURED, INTERPOLATED, HELD, LEFT = 0, 1, 2, 3
 UNREPAIRABLE = sb.UNREPAIRABLE
 QUIET_NAN = np.array([0x7ff8000000000000], np.uint64).view(np.float64)[0]
 
-HEADER_PATH = os.path.join(os.path.dirname(_lib.HEADER_PATH), "p2r_recording_repair.h")
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(_lib.__file__)), "libp2r_recording_repair.so")
-_rr_lib = None
+_library = _lib.extension("recording_repair")
+HEADER_PATH, LIB_PATH = _library.header_path, _library.lib_path
+lib, _launch = _library.lib, _library.launch
 
 
 class RepairSpec(collections.namedtuple("RepairSpec", "max_gap hold_ends smooth")):
@@ -57,31 +56,6 @@ def _spec(spec, who):
     if not isinstance(spec, RepairSpec):
         raise TypeError(f"{who}: spec must be a RepairSpec, got {type(spec).__name__}")
     return spec
-
-
-def lib():
-    """libp2r_recording_repair.so with the argtypes of include/p2r_recording_repair.h; a missing library is an error (no
-    fallback)."""
-    global _rr_lib
-    if _rr_lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise _lib.P2RLibraryError(f"{LIB_PATH} is missing: build it with `make -C pose2room_amd/csrc` "
-                                       "(pose2room_amd has no CPU fallback)")
-        l = ctypes.CDLL(LIB_PATH)
-        for name, proto in _lib.prototypes(HEADER_PATH).items():
-            fn = getattr(l, name)
-            fn.restype, fn.argtypes = proto.restype, proto.argtypes
-        _rr_lib = l
-    return _rr_lib
-
-
-def _launch(name, device, *args):
-    """entry point `name` on the current stream of `device`: tensors as their address, None as NULL"""
-    fn = getattr(lib(), name)
-    if len(args) + 1 != len(fn.argtypes):
-        raise TypeError(f"{name}: {len(args)} arguments for {len(fn.argtypes) - 1} parameters in front of the stream")
-    with torch.cuda.device(device):
-        _lib.check(fn(*[a.data_ptr() if torch.is_tensor(a) else a for a in args], _lib.current_stream(device)), name)
 
 
 # ---- the contract in NumPy ------------------------------------------------------------------------------------------

@@ -27,7 +27,6 @@ No CPU fallback: the mirror is what the tests compare against, not a second impl
 """
 import collections
 import ctypes
-import os
 
 import numpy as np
 import torch
@@ -43,36 +42,11 @@ STATUS_NO_ROOM, STATUS_NO_OBJECT, STATUS_NON_FINITE = 1, 2, 4
 FLIP = np.array([[0, 0, 1], [0, 1, 0], [1, 0, 0]])           # swaps x and z
 ROT90 = np.array([[0, 0, -1], [0, 1, 0], [1, 0, 0]])         # (x, y, z) -> (z, y, -x) as a row vector times it
 
-HEADER_PATH = os.path.join(os.path.dirname(_lib.HEADER_PATH), "p2r_sample_build.h")
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(_lib.__file__)), "libp2r_sample_build.so")
-_sb_lib = None
-_Recordings = _lib.struct('p2r_recordings', HEADER_PATH)
-_Plan = _lib.struct('p2r_sample_plan', HEADER_PATH)
-
-
-def lib():
-    """libp2r_sample_build.so with the argtypes of include/p2r_sample_build.h; a missing library is an error (no
-    fallback)."""
-    global _sb_lib
-    if _sb_lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise _lib.P2RLibraryError(f"{LIB_PATH} is missing: build it with `make -C pose2room_amd/csrc` "
-                                       "(pose2room_amd has no CPU fallback)")
-        l = ctypes.CDLL(LIB_PATH)
-        for name, proto in _lib.prototypes(HEADER_PATH).items():
-            fn = getattr(l, name)
-            fn.restype, fn.argtypes = proto.restype, proto.argtypes
-        _sb_lib = l
-    return _sb_lib
-
-
-def _launch(name, device, *args):
-    """entry point `name` on the current stream of `device`: tensors as their address, None as NULL"""
-    fn = getattr(lib(), name)
-    if len(args) + 1 != len(fn.argtypes):
-        raise TypeError(f"{name}: {len(args)} arguments for {len(fn.argtypes) - 1} parameters in front of the stream")
-    with torch.cuda.device(device):
-        _lib.check(fn(*[a.data_ptr() if torch.is_tensor(a) else a for a in args], _lib.current_stream(device)), name)
+_library = _lib.extension("sample_build")
+HEADER_PATH, LIB_PATH = _library.header_path, _library.lib_path
+lib, _launch = _library.lib, _library.launch
+_Recordings = _library.struct('p2r_recordings')
+_Plan = _library.struct('p2r_sample_plan')
 
 
 def _config():

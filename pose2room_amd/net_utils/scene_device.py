@@ -18,9 +18,6 @@ host loop per sample and per object.  Here it is three launches for the whole ba
 `P2RNet.predict_scenes` is the public entry.  `SceneBatch` holds the device tensors and crosses to the host once, when a
 caller asks for dicts, records or files.  No CPU fallback.
 """
-import ctypes
-import os
-
 import numpy as np
 import torch
 
@@ -30,34 +27,10 @@ MAX_K, MAX_T, MAX_J = 1024, 65535, 64      # P2R_SCENE_MAX_K / _T / _J of includ
 UNIQUE_MAX_T = 4096                        # P2R_UNIQUE_MAX_T: three int tables of T entries in LDS
 
 # The kernels are a library of their own next to libp2r_hip.so (csrc/Makefile), with a header of their own; the binding
-# is derived from that header by the parser that binds libp2r_hip.so (_lib.prototypes).
-HEADER_PATH = os.path.join(os.path.dirname(_lib.HEADER_PATH), "p2r_scene.h")
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(_lib.__file__)), "libp2r_scene.so")
-_scene_lib = None
-
-
-def lib():
-    """libp2r_scene.so with the argtypes of include/p2r_scene.h; a missing library is an error (no fallback)."""
-    global _scene_lib
-    if _scene_lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise _lib.P2RLibraryError(f"{LIB_PATH} is missing: build it with `make -C pose2room_amd/csrc` "
-                                       "(pose2room_amd has no CPU fallback)")
-        l = ctypes.CDLL(LIB_PATH)
-        for name, proto in _lib.prototypes(HEADER_PATH).items():
-            fn = getattr(l, name)
-            fn.restype, fn.argtypes = proto.restype, proto.argtypes
-        _scene_lib = l
-    return _scene_lib
-
-
-def _launch(name, device, *args):
-    """entry point `name` on the current stream of `device`: tensors as their address"""
-    fn = getattr(lib(), name)
-    if len(args) + 1 != len(fn.argtypes):
-        raise TypeError(f"{name}: {len(args)} arguments for {len(fn.argtypes) - 1} parameters in front of the stream")
-    with torch.cuda.device(device):
-        _lib.check(fn(*[a.data_ptr() if torch.is_tensor(a) else a for a in args], _lib.current_stream(device)), name)
+# is derived from that header as that of libp2r_hip.so is (_lib.Library).
+_library = _lib.extension("scene")
+HEADER_PATH, LIB_PATH = _library.header_path, _library.lib_path
+lib, _launch = _library.lib, _library.launch
 
 
 def _want(what, name, t, dtype, shape):

@@ -16,7 +16,6 @@ that is `|R (p - c)| <= size / 2 + contact_dist` per axis, which is what the ker
 No CPU fallback: the mirror is what the tests compare against, not a second implementation behind the op.
 """
 import ctypes
-import os
 
 import numpy as np
 import torch
@@ -27,36 +26,11 @@ MAX_K = 256                     # box slots per sample (include/p2r_vote_labels.
 ORTHONORMAL_TOL = 1e-6          # |R R^T - I| above this: the hull test and the closed form need not agree
 
 # The kernels are a fourth library next to libp2r_hip.so (csrc/Makefile), with a header of their own; the binding is
-# derived from that header by the parser that binds libp2r_hip.so (_lib.prototypes, _lib.struct).
-HEADER_PATH = os.path.join(os.path.dirname(_lib.HEADER_PATH), "p2r_vote_labels.h")
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(_lib.__file__)), "libp2r_vote_labels.so")
-_vl_lib = None
-_Boxes = _lib.struct('p2r_contact_boxes', HEADER_PATH)
-
-
-def lib():
-    """libp2r_vote_labels.so with the argtypes of include/p2r_vote_labels.h; a missing library is an error (no
-    fallback)."""
-    global _vl_lib
-    if _vl_lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise _lib.P2RLibraryError(f"{LIB_PATH} is missing: build it with `make -C pose2room_amd/csrc` "
-                                       "(pose2room_amd has no CPU fallback)")
-        l = ctypes.CDLL(LIB_PATH)
-        for name, proto in _lib.prototypes(HEADER_PATH).items():
-            fn = getattr(l, name)
-            fn.restype, fn.argtypes = proto.restype, proto.argtypes
-        _vl_lib = l
-    return _vl_lib
-
-
-def _launch(name, device, *args):
-    """entry point `name` on the current stream of `device`: tensors as their address"""
-    fn = getattr(lib(), name)
-    if len(args) + 1 != len(fn.argtypes):
-        raise TypeError(f"{name}: {len(args)} arguments for {len(fn.argtypes) - 1} parameters in front of the stream")
-    with torch.cuda.device(device):
-        _lib.check(fn(*[a.data_ptr() if torch.is_tensor(a) else a for a in args], _lib.current_stream(device)), name)
+# derived from that header as that of libp2r_hip.so is (_lib.Library).
+_library = _lib.extension("vote_labels")
+HEADER_PATH, LIB_PATH = _library.header_path, _library.lib_path
+lib, _launch = _library.lib, _library.launch
+_Boxes = _library.struct('p2r_contact_boxes')
 
 
 def default_contact_dist():

@@ -19,9 +19,7 @@ optimizer reads there.
 `grad_guard_reference` is the contract in float64 on the host; the tests compare the kernels with it.  There is no CPU
 fallback: parameters on the CPU are refused, a missing library is a `P2RLibraryError`.
 """
-import ctypes
 import math
-import os
 
 import torch
 
@@ -32,33 +30,14 @@ GROUP = 160             # P2R_GG_GROUP: table entries per launch
 NONFINITE = ('ignore', 'skip', 'raise')
 _DTYPES = {torch.float32: 0, torch.float64: 1}      # P2R_GG_F32, P2R_GG_F64
 
-HEADER_PATH = os.path.join(os.path.dirname(_lib.HEADER_PATH), "p2r_grad_guard.h")
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(_lib.__file__)), "libp2r_grad_guard.so")
-_gg_lib = None
-_entry_type = None
-
-
-def lib():
-    """libp2r_grad_guard.so with the argtypes of include/p2r_grad_guard.h; a missing library is an error (no fallback)."""
-    global _gg_lib
-    if _gg_lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise _lib.P2RLibraryError(f"{LIB_PATH} is missing: build it with `make -C pose2room_amd/csrc` "
-                                       "(pose2room_amd has no CPU fallback)")
-        l = ctypes.CDLL(LIB_PATH)
-        for name, proto in _lib.prototypes(HEADER_PATH).items():
-            fn = getattr(l, name)
-            fn.restype, fn.argtypes = proto.restype, proto.argtypes
-        _gg_lib = l
-    return _gg_lib
+_library = _lib.extension("grad_guard")
+HEADER_PATH, LIB_PATH = _library.header_path, _library.lib_path
+lib = _library.lib
 
 
 def entry_type():
     """the ctypes.Structure of p2r_grad_entry, from the header"""
-    global _entry_type
-    if _entry_type is None:
-        _entry_type = _lib.struct("p2r_grad_entry", HEADER_PATH)
-    return _entry_type
+    return _library.struct("p2r_grad_entry")
 
 
 # ---- the contract ---------------------------------------------------------------------------------------------------------
@@ -174,12 +153,9 @@ def measure(grads, max_norm, count_skips=False, out=None, device=None, names=Non
     elif out.n != len(grads) or out.chunks != chunks or out.device != dev:
         raise ValueError(f"grad_guard.measure: `out` was made for {out.n} gradients in {out.chunks} chunks on {out.device}, "
                          f"got {len(grads)} in {chunks} on {dev}")
-    fn = lib().p2r_grad_measure
-    with torch.cuda.device(dev):
-        _lib.check(fn(table, len(grads), float(max_norm), int(bool(count_skips)), chunks, out.part_sumsq.data_ptr(),
-                      out.part_count.data_ptr(), out.first_chunk.data_ptr(), out.sumsq.data_ptr(),
-                      out.nonfinite.data_ptr(), out.norm.data_ptr(), out.scale.data_ptr(), out.found.data_ptr(),
-                      out.steps.data_ptr(), out.skipped.data_ptr(), _lib.current_stream(dev)), "p2r_grad_measure")
+    _library.launch("p2r_grad_measure", dev, table, len(grads), float(max_norm), int(bool(count_skips)), chunks,
+                    out.part_sumsq, out.part_count, out.first_chunk, out.sumsq, out.nonfinite, out.norm, out.scale,
+                    out.found, out.steps, out.skipped)
     return out
 
 
@@ -191,8 +167,7 @@ def scale_grads(grads, scale, names=None):
         return
     if not (torch.is_tensor(scale) and scale.dtype == torch.float32 and scale.numel() == 1 and scale.device == dev):
         raise ValueError(f"grad_guard.scale_grads: scale must be one float32 on {dev}")
-    with torch.cuda.device(dev):
-        _lib.check(lib().p2r_grad_scale(table, len(grads), scale.data_ptr(), _lib.current_stream(dev)), "p2r_grad_scale")
+    _library.launch("p2r_grad_scale", dev, table, len(grads), scale)
 
 
 # ---- the guard --------------------------------------------------------------------------------------------------------------

@@ -229,8 +229,8 @@ def test_wrappers_refuse_cpu_tensors_and_bad_shapes():
 
 
 def test_a_missing_library_is_an_error(monkeypatch):
-    monkeypatch.setattr(cd, 'LIB_PATH', os.path.join(os.path.dirname(cd.LIB_PATH), 'libp2r_consensus_absent.so'))
-    monkeypatch.setattr(cd, '_consensus_lib', None)
+    monkeypatch.setattr(cd._library, 'lib_path', os.path.join(os.path.dirname(cd.LIB_PATH), 'libp2r_consensus_absent.so'))
+    monkeypatch.setattr(cd._library, '_handle', None)
     with pytest.raises(_lib.P2RLibraryError, match="libp2r_consensus_absent.so is missing"):
         cd.lib()
 

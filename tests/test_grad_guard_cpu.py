@@ -232,8 +232,8 @@ def test_entry_points_refuse_bad_arguments():
 
 
 def test_a_missing_library_is_an_error(monkeypatch):
-    monkeypatch.setattr(gg, 'LIB_PATH', os.path.join(os.path.dirname(gg.LIB_PATH), 'libp2r_grad_guard_absent.so'))
-    monkeypatch.setattr(gg, '_gg_lib', None)
+    monkeypatch.setattr(gg._library, 'lib_path', os.path.join(os.path.dirname(gg.LIB_PATH), 'libp2r_grad_guard_absent.so'))
+    monkeypatch.setattr(gg._library, '_handle', None)
     with pytest.raises(_lib.P2RLibraryError, match="libp2r_grad_guard_absent.so is missing"):
         gg.lib()
 

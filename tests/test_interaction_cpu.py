@@ -311,8 +311,8 @@ def test_default_contact_thresh_is_the_training_labels_distance(monkeypatch):
 
 
 def test_a_missing_library_is_an_error(monkeypatch):
-    monkeypatch.setattr(idv, 'LIB_PATH', os.path.join(os.path.dirname(idv.LIB_PATH), 'libp2r_interaction_absent.so'))
-    monkeypatch.setattr(idv, '_interaction_lib', None)
+    monkeypatch.setattr(idv._library, 'lib_path', os.path.join(os.path.dirname(idv.LIB_PATH), 'libp2r_interaction_absent.so'))
+    monkeypatch.setattr(idv._library, '_handle', None)
     with pytest.raises(_lib.P2RLibraryError, match="libp2r_interaction_absent.so is missing"):
         idv.lib()
 

@@ -302,8 +302,8 @@ def test_wrappers_refuse_cpu_tensors_and_bad_shapes():
 
 
 def test_a_missing_library_is_an_error(monkeypatch):
-    monkeypatch.setattr(od, 'LIB_PATH', os.path.join(os.path.dirname(od.LIB_PATH), 'libp2r_occupancy_absent.so'))
-    monkeypatch.setattr(od, '_occupancy_lib', None)
+    monkeypatch.setattr(od._library, 'lib_path', os.path.join(os.path.dirname(od.LIB_PATH), 'libp2r_occupancy_absent.so'))
+    monkeypatch.setattr(od._library, '_handle', None)
     with pytest.raises(_lib.P2RLibraryError, match="libp2r_occupancy_absent.so is missing"):
         od.lib()
 

@@ -208,8 +208,8 @@ def test_wrappers_refuse_cpu_tensors_and_bad_shapes():
 
 
 def test_a_missing_library_is_an_error(monkeypatch):
-    monkeypatch.setattr(sd, 'LIB_PATH', os.path.join(os.path.dirname(sd.LIB_PATH), 'libp2r_scene_absent.so'))
-    monkeypatch.setattr(sd, '_scene_lib', None)
+    monkeypatch.setattr(sd._library, 'lib_path', os.path.join(os.path.dirname(sd.LIB_PATH), 'libp2r_scene_absent.so'))
+    monkeypatch.setattr(sd._library, '_handle', None)
     with pytest.raises(_lib.P2RLibraryError, match="libp2r_scene_absent.so is missing"):
         sd.lib()
 

@@ -7,7 +7,7 @@ import torch, numpy as np
 from pose2room_amd.p2rnet import gcn_op, gcn_tables
 from pose2room_amd.p2rnet.modules.stgcn_layers import Graph
 from pose2room_amd import _lib
-_lib.LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ubench", "libp2r_hip_trace.so")
+_lib.main.lib_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ubench", "libp2r_hip_trace.so")
 dev = torch.device('cuda:0')
 A = Graph().A
 K, V = A.shape[0], A.shape[1]

@@ -6,7 +6,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, numpy as np
 from pose2room_amd.p2rnet import tconv_op
 from pose2room_amd import _lib
-_lib.LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ubench", "libp2r_hip_trace.so")
+_lib.main.lib_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ubench", "libp2r_hip_trace.so")
 dev = torch.device('cuda:0')
 N, T, V = 32, 1024, 53
 g = torch.Generator().manual_seed(0)
